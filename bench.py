@@ -10,9 +10,12 @@ rank 0 when N > 1, and the finish on rank 0 (merged reduce, radix sort by
 first occurrence, key decode): the ordered Map-equivalent result, in HBM.
 
 value = windows examined on both strands (k-mers) per second,
-whole job.  Also reported: distinct k-mers/s, the tile kernel's roofline
-(algorithmic bytes / kernel time vs 8 TB/s HBM), and the CPU baseline (the
-oracle restatement, 1 core, bounded sample).
+whole job.  A plain run sets up, warms up, times the steps and prints that
+line.  --dump-outputs DIR also writes the last timed step's result as .npy
+files.  --full adds everything else: distinct k-mers/s, the tile kernel's
+roofline (algorithmic bytes / kernel time vs 8 TB/s HBM), the two-session
+throughput, the PCIe-inclusive and end-to-end rates, template matching and
+the CPU baseline (the oracle restatement, 1 core, bounded sample).
 """
 import argparse
 import json
@@ -277,6 +280,77 @@ def table_phase_bytes(nbytes, n_keys, canonical, key_bytes=8):
             "scatter2": 2 * kb * n_keys, "final": kb * n_keys + 8 * canonical}
 
 
+DUMP_BUDGET = 60 << 20      # bytes of array data --dump-outputs writes, all files and ranks together
+
+
+def sample_rows(n, row_bytes, budget):
+    """Rows of an n-row output to dump: all of them, or the fixed (seed 0),
+    sorted sample of as many as fit `budget` bytes."""
+    import numpy as np
+    m = max(0, budget // row_bytes)
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, size=m, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, ctr, k, table, rank, world, dev, has_result):
+    """--dump-outputs: what the last timed step left for its caller, as
+    DIR/<name>.npy (float32 / float64; `.rank<r>` before .npy when N > 1).
+
+    ordered paths -- the device result (kmer_result_device) and the host-side
+    record keys (kmer_records_export, rank 0):
+      rows    indices of the dumped entries (all, or the seeded sample)
+      keys    [rows, k] key bytes           counts, firsts  [rows]
+      record_keys (flat bytes), record_offsets, record_counts, record_firsts
+      totals  [entries, sum of counts, record keys, sum of record counts]
+    No empty array is written: without record keys (or entries) those files
+    are left out, and `totals` says so.
+    table mode: table [canonical k-mers, Map keys, sum of Map counts,
+      digest >> 32, digest & 0xffffffff] (kmer_table_stats, kmer_table_digest)."""
+    import numpy as np
+    import torch
+    from kmerjs_amd.multi import _CudaArray, device_u64
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else ".rank%d" % rank
+    budget = DUMP_BUDGET // world
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + tag + ".npy"), a)
+
+    if table:
+        canonical, n_keys, map_sum = ctr.table_stats()
+        d = ctr.table_digest()
+        save("table", np.array([canonical, n_keys, map_sum, d >> 32, d & 0xffffffff], dtype=np.float64))
+        return
+    f64 = lambda a: np.asarray(a).view(np.uint64).astype(np.float64)   # noqa: E731
+    # record keys: all of them, or the leading ones that fit a quarter of the budget
+    n_rec, rec_sum = 0, 0
+    if rank == 0:
+        kb, off, rcnt, rfirst = ctr.records_export()
+        n_rec, rec_sum = len(rcnt), int(rcnt.sum())
+        cost = 4 * off[1:].astype(np.int64) + 24 * np.arange(1, n_rec + 1, dtype=np.int64)
+        m = int(np.searchsorted(cost, budget // 4, side="right"))
+        if m:
+            save("record_keys", np.frombuffer(kb, dtype=np.uint8)[:int(off[m])].astype(np.float32))
+            save("record_offsets", f64(off[:m + 1]))
+            save("record_counts", f64(rcnt[:m]))
+            save("record_firsts", f64(rfirst[:m]))
+            budget -= int(cost[m - 1])
+    d_keys, d_cnt, d_first, n = ctr.result_device() if has_result else (0, 0, 0, 0)
+    rows = sample_rows(n, 24 + 4 * k, budget)
+    dev_sum = 0
+    if n:
+        ti = torch.from_numpy(rows).to(dev)
+        keys = torch.as_tensor(_CudaArray(d_keys, n * k, "|u1"), device=dev).view(n, k)
+        cnt, fst = device_u64(d_cnt, n, dev), device_u64(d_first, n, dev)
+        dev_sum = int(cnt.sum().item())
+        save("keys", keys[ti].cpu().numpy().astype(np.float32))
+        save("counts", f64(cnt[ti].cpu().numpy()))
+        save("firsts", f64(fst[ti].cpu().numpy()))
+        save("rows", rows.astype(np.float64))
+    save("totals", np.array([n, dev_sum, n_rec, rec_sum], dtype=np.float64))
+
+
 def print_shard_plan(args, world, strong):
     """--dry-run: the record-aligned shard each rank would count (reads-based
     configs: multi.shard_plan; c5: the rank's own contig file), one JSON line
@@ -368,13 +442,23 @@ def main():
     ap.add_argument("--prefix", default="ATGAC")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--flags", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the Node readFile() -> Map end-to-end run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's result to DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: a fixed seeded sample of a larger result; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and report everything beside the headline: result "
+                         "size and distinct k-mers/s, roofline of the dominant kernel, two-session throughput, "
+                         "PCIe-inclusive and end-to-end rates, template matching, CPU baselines (the --no-* "
+                         "options switch single legs off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive count")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full: skip the Node readFile() -> Map end-to-end run")
     ap.add_argument("--no-pipelined", action="store_true",
-                    help="skip the extra two-session (double-buffered) throughput measurement")
+                    help="--full: skip the extra two-session (double-buffered) throughput measurement")
     ap.add_argument("--no-match", action="store_true",
-                    help="skip the template-matching record (C2's result joined against a synthetic kmerFinder DB)")
+                    help="--full: skip the template-matching record (C2's result joined against a synthetic "
+                         "kmerFinder DB)")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="sessions in rotation (>= 2: a step's finish overlaps the next steps' scans)")
     ap.add_argument("--config", default="c2", choices=("c1", "c2", "c3", "c4", "c5"),
@@ -570,6 +654,67 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        # the session that ran the last timed step still holds its result
+        dump_outputs(args.dump_outputs, ctrs[(args.steps - 1) % nctx], args.k, table, rank, world, dev,
+                     rank == 0 or args.merge != "gather")
+
+    windows_step = wl["windows_total"]
+    ms_per_step = elapsed / args.steps * 1e3
+    value = windows_step * args.steps / elapsed
+    coll = "RCCL" if rccl_ranks else (dist.get_backend().upper() if world > 1 else "")
+    out = {
+        "metric": "k-mers/sec + distinct-kmers/sec, k=%d 150bp synthetic FASTQ, 1/2/4/8 GPU" % args.k,
+        "value": value,
+        "unit": "k-mers/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": {"c1": "test_data/test_short.fastq (reference fixture)",
+                 "c5": "synthetic contigs (numpy PCG64, seed 5 + rank)%s" % (
+                     ", 60-column FASTA records" if args.fasta else "")}.get(
+                     args.config, "synthetic (on-device splitmix64 FASTQ, 317 B records, seed %d)" % args.seed),
+        "config": {"workload": wl["desc"], "name": args.config,
+                   "reads_per_gpu": args.reads if args.config in ("c2", "c3", "c4") else None,
+                   "mode": ("table, canonical k-mers (KMER_FLAG_CANONICAL)" if args.flags & _FC else
+                            "table (unordered canonical counts, KMER_FLAG_UNORDERED)") if table
+                           else "ordered (reference Map insertion order)",
+                   "k": args.k, "prefix": args.prefix, "windows_per_step": windows_step,
+                   "bytes_per_gpu": nbytes,
+                   "pipeline": ("%d sessions in rotation: finishes overlap later scans" % nctx if nctx > 1
+                                else "off (steps in sequence)"),
+                   "parallelism": "dp1 (one GPU; no collective)" if world == 1 else
+                   "dp%d (reads sharded; %s%s%s)" % (
+                       world, coll + " all-to-all of pass-1 keys by hash-space slice, per-rank table finish"
+                       if table else {"hits": coll + " all-to-all of hits by key range, per-rank finish",
+                    "alltoall": coll + " all-to-all of partials by key range, per-rank finish",
+                    "dense": coll + " reduce-scatter of dense count / first-occurrence arrays, per-rank finish"}.get(
+                        args.merge, coll + " gather of partials, finish on rank 0"),
+                       "; + alltoallv gather of the ordered ranges to rank 0 and device merge into one "
+                       "Map-order result" if args.collect else "",
+                       "; REHEARSAL: every rank on device 0" if one_device else ""),
+                   "backend": "none" if world == 1 else ("rccl" if rccl_ranks else dist.get_backend())},
+        "rccl_ranks": rccl_ranks,
+    }
+
+    def close_all():
+        for c in ctrs:
+            c.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: the headline needs nothing more
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        close_all()
+        return
+
     # Also measured (single GPU, ordered paths): the same K steps with two
     # sessions in rotation, each step's finish overlapping the next step's
     # scan -- the double-buffered throughput of a batch pipeline.  Reported
@@ -669,9 +814,6 @@ def main():
                   % (want_d, list(want_s), world), file=sys.stderr)
 
     if rank == 0:
-        windows_step = wl["windows_total"]
-        ms_per_step = elapsed / args.steps * 1e3
-        value = windows_step * args.steps / elapsed
         kern_ms = sum(tile_ms) / len(tile_ms)
         # step-level fraction: SURVEY.md §8d algorithmic bytes per window (input
         # B_in + table B_table) x windows of the step / step time
@@ -745,44 +887,7 @@ def main():
             algo_bytes = nbytes + 24 * (accepted / world)
         achieved = algo_bytes / (kern_ms * 1e-3) / 1e9
         traffic = load_traffic(args, kern_name)
-        coll = "RCCL" if rccl_ranks else (dist.get_backend().upper() if world > 1 else "")
-        out = {
-            "metric": "k-mers/sec + distinct-kmers/sec, k=%d 150bp synthetic FASTQ, 1/2/4/8 GPU" % args.k,
-            "value": value,
-            "unit": "k-mers/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": {"c1": "test_data/test_short.fastq (reference fixture)",
-                     "c5": "synthetic contigs (numpy PCG64, seed 5 + rank)%s" % (
-                         ", 60-column FASTA records" if args.fasta else "")}.get(
-                         args.config, "synthetic (on-device splitmix64 FASTQ, 317 B records, seed %d)" % args.seed),
-            "config": {"workload": wl["desc"], "name": args.config,
-                       "reads_per_gpu": args.reads if args.config in ("c2", "c3", "c4") else None,
-                       "mode": ("table, canonical k-mers (KMER_FLAG_CANONICAL)" if args.flags & _FC else
-                                "table (unordered canonical counts, KMER_FLAG_UNORDERED)") if table
-                               else "ordered (reference Map insertion order)",
-                       "k": args.k, "prefix": args.prefix, "windows_per_step": windows_step,
-                       "bytes_per_gpu": nbytes,
-                       "pipeline": ("%d sessions in rotation: finishes overlap later scans" % nctx if nctx > 1
-                                    else "off (steps in sequence)"),
-                       "parallelism": "dp1 (one GPU; no collective)" if world == 1 else
-                       "dp%d (reads sharded; %s%s%s)" % (
-                           world, coll + " all-to-all of pass-1 keys by hash-space slice, per-rank table finish"
-                           if table else {"hits": coll + " all-to-all of hits by key range, per-rank finish",
-                        "alltoall": coll + " all-to-all of partials by key range, per-rank finish",
-                        "dense": coll + " reduce-scatter of dense count / first-occurrence arrays, per-rank finish"}.get(
-                            args.merge, coll + " gather of partials, finish on rank 0"),
-                           "; + alltoallv gather of the ordered ranges to rank 0 and device merge into one "
-                           "Map-order result" if args.collect else "",
-                           "; REHEARSAL: every rank on device 0" if one_device else ""),
-                       "backend": "none" if world == 1 else ("rccl" if rccl_ranks else dist.get_backend())},
-            "rccl_ranks": rccl_ranks,
+        out.update({
             "distinct_kmers_per_s": distinct * args.steps / elapsed,
             "distinct_kmers": distinct,
             "accepted_windows": accepted,
@@ -792,7 +897,7 @@ def main():
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kern_name,
                          "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kern_ms,
                          "step_frac": step_frac, "step_bytes_per_window": b_in + b_table},
-        }
+        })
         if verified_table is not None:
             out["verified_table"] = verified_table
         if phases is not None:
@@ -829,10 +934,7 @@ def main():
             out["template_matching"] = bench_match.measure(d_keys, d_cnt, nq, args.k, args.reads,
                                                            cpu_baseline=not args.no_cpu_baseline)
         print(json.dumps(out), flush=True)
-    for c in ctrs:
-        c.close()
-    if world > 1:
-        dist.destroy_process_group()
+    close_all()
 
 
 if __name__ == "__main__":

@@ -36,6 +36,18 @@ def test_count_windows_line_phase(first_line):
     assert got == want
 
 
+def test_sample_rows_is_fixed_and_fits():
+    """--dump-outputs: a result within the budget is dumped whole, a larger one
+    as the same sorted sample of distinct rows on every run."""
+    import numpy as np
+    assert bench.sample_rows(10, 8, 80).tolist() == list(range(10))
+    a, b = bench.sample_rows(1000, 8, 800), bench.sample_rows(1000, 8, 800)
+    assert a.tolist() == b.tolist() and len(a) == 100
+    assert bool((np.diff(a) > 0).all()) and 0 <= a[0] and a[-1] < 1000
+    # the C2 result (~2 M entries of 24 + 4 k bytes) stays under 64 MB in all
+    assert len(bench.sample_rows(2_000_000, 24 + 4 * 16, bench.DUMP_BUDGET)) * 88 <= 64 << 20
+
+
 def test_gpus_n_launches_n_ranks_dry_run():
     """`bench.py --gpus N` with no launcher starts ranks 0..N-1 itself (VERDICT r3
     weak #1): the dry run prints the environment of each rank it would start."""

@@ -7,7 +7,7 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 TAG=$1; shift
 mkdir -p gpurun_out/$TAG
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-match --no-pcie --no-pipelined"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-match --no-pcie --no-pipelined"
 i=0
 for v in "$@"; do
   i=$((i+1))

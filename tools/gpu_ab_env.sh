@@ -7,7 +7,7 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 TAG=$1; ARGS=$2; shift 2
 mkdir -p gpurun_out/$TAG
-B="python bench.py --no-cpu-baseline --no-e2e --no-match --no-pcie --no-pipelined $ARGS"
+B="python bench.py --full --no-cpu-baseline --no-e2e --no-match --no-pcie --no-pipelined $ARGS"
 for v in "$@"; do
   name=${v%%:*}
   if [ "$name" = "$v" ]; then

@@ -5,7 +5,7 @@
 set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/chk
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-match --no-pcie"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-match --no-pcie"
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread \
     > gpurun_out/chk/pytest.txt 2>&1 || { tail -30 gpurun_out/chk/pytest.txt; exit 1; }
 tail -2 gpurun_out/chk/pytest.txt

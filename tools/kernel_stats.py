@@ -1,8 +1,9 @@
-"""Per-kernel duration statistics of the TIMED steps of a bench.py run under
-`rocprofv3 --kernel-trace` (profiles/ evidence).
+"""Per-kernel duration statistics of the TIMED steps of a `bench.py --full` run
+under `rocprofv3 --kernel-trace` (profiles/ evidence).
 
-bench.py runs W warmup steps, K timed steps, then one more step (E = 1) that
-reads the result size outside the timed region; with its side legs switched
+bench.py --full runs W warmup steps, K timed steps, then one more step (E = 1)
+that reads the result size outside the timed region (a plain run, without
+--full, stops after the timed steps: E = 0); with its side legs switched
 off (--no-pcie --no-e2e --no-pipelined --no-match --no-cpu-baseline) every
 kernel is dispatched the same number of times per step, so the timed steps are
 the K x per dispatches before the last E x per, per = (dispatches - E) /

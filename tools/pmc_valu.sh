@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 C="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE"
-B="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pcie --no-e2e --no-match --no-pipelined"
+B="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-pcie --no-e2e --no-match --no-pipelined"
 timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/ship" -o run -- python3 $B > "$OUT/ship.log" 2>&1 || exit 1
 KMERHIP_LIB_EXPERIMENT=kmerjs_amd/libkmerhip_exp.so timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace --output-format csv \
     -d "$OUT/abl" -o run -- python3 $B --flags 256 > "$OUT/abl.log" 2>&1 || exit 1

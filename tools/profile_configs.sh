@@ -22,7 +22,7 @@ for cfg in "$@"; do
     k64AT) W=1; K=3; A="--k 64 --prefix AT --reads 2000000" ;;
   esac
   timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$cfg -o run -- \
-      python3 bench.py --steps $K --warmup $W $NOX $A > $O/trace_$cfg.log 2>&1 || exit $?
+      python3 bench.py --full --steps $K --warmup $W $NOX $A > $O/trace_$cfg.log 2>&1 || exit $?
   python3 tools/kernel_stats.py $O/trace_$cfg $W $K $O/${cfg}_kernel_stats.csv || exit $?
   # the bench line of the SAME run (HIP events) next to rocprof's average of
   # its dominant kernel over the same timed steps

@@ -13,7 +13,7 @@ mkdir -p gpurun_out/reh
 export KMERHIP_ONE_DEVICE=1 KMERHIP_DIST_BACKEND=gloo KMERHIP_BENCH_VERIFY=1
 run() {   # name args...
   local n=$1; shift
-  timeout -k 10 240 python bench.py --gpus 2 --steps 3 --warmup 1 "$@" \
+  timeout -k 10 240 python bench.py --full --gpus 2 --steps 3 --warmup 1 "$@" \
       > gpurun_out/reh/$n.json 2> gpurun_out/reh/$n.err || { echo "$n failed"; tail -5 gpurun_out/reh/$n.err; exit 1; }
   grep -h "verify" gpurun_out/reh/$n.err > gpurun_out/reh/$n.verify.txt || { echo "$n: no verify line"; exit 1; }
   echo "$n ok: $(cat gpurun_out/reh/$n.verify.txt)"

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 run() {
     local name=$1
     shift
-    timeout -k 10 400 python bench.py "$@" > "$OUT/$name.log" 2>&1
+    timeout -k 10 400 python bench.py --full "$@" > "$OUT/$name.log" 2>&1
     local rc=$?
     grep '^{' "$OUT/$name.log" > "$OUT/$name.json" || true
     echo "$name rc=$rc"

@@ -11,6 +11,6 @@ timeout -k 10 780 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 tail -3 "$OUT/pytest_gpu.txt"
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" \
     > "$OUT/smoke.txt" 2>&1 || { echo "smoke rc=$?"; exit 1; }
-timeout -k 10 300 python bench.py > "$OUT/bench_default.log" 2>&1 || { echo "bench rc=$?"; exit 1; }
+timeout -k 10 300 python bench.py --full > "$OUT/bench_default.log" 2>&1 || { echo "bench rc=$?"; exit 1; }
 grep '^{' "$OUT/bench_default.log" > "$OUT/bench_default.json" || true
 cat "$OUT/bench_default.json"
