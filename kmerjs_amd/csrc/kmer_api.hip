@@ -195,13 +195,25 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
         c->d_line_count = (unsigned long long *)(c->d_scal + 6);
         c->d_ends_open = (unsigned long long *)(c->d_scal + 7);
     }
+    ok &= dalloc(&c->d_stamp, STAMP_WORDS) == hipSuccess;
+    if (ok) ok &= hipMemset(c->d_stamp, 0, STAMP_WORDS * sizeof(uint64_t)) == hipSuccess;
+    {
+        int khz = 0;
+        ok &= hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0;
+        c->clock_khz = khz;
+    }
+    if (const char *e = exp_env("KMERHIP_TIMING"))     // (A/B experiments: events = as before, none = no records)
+        c->tmode = strcmp(e, "events") == 0 ? kmer_ctx::TIME_EVENTS
+                   : strcmp(e, "none") == 0 ? kmer_ctx::TIME_NONE : kmer_ctx::TIME_STAMPS;
+    if (const char *e = exp_env("KMERHIP_BKT_ROUTE"))  // (counted: the three-kernel partition from the start)
+        c->bkt_counted = strcmp(e, "counted") == 0;
     ok &= dalloc(&c->d_pos, 1) == hipSuccess;
     ok &= dalloc(&c->d_pos_saved, 1) == hipSuccess;
     ok &= hipHostMalloc((void **)&c->h_small, 24 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    ok &= hipHostMalloc((void **)&c->h_tail, 16 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent) ==
+    ok &= hipHostMalloc((void **)&c->h_tail, TAIL_WORDS * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent) ==
           hipSuccess;
     ok &= c->h_tail && hipHostGetDevicePointer((void **)&c->d_tail, c->h_tail, 0) == hipSuccess;
-    if (c->h_tail) memset(c->h_tail, 0, 16 * sizeof(uint64_t));
+    if (c->h_tail) memset(c->h_tail, 0, TAIL_WORDS * sizeof(uint64_t));
     for (hipEvent_t &e : c->tev) ok &= hipEventCreate(&e) == hipSuccess;
     for (hipEvent_t &e : c->fa_ev) ok &= hipEventCreate(&e) == hipSuccess;
     ok &= hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
@@ -246,6 +258,7 @@ kmer_status kmer_close(kmer_ctx *c) {
         b->release();
     for (auto *b : {&c->ridx, &c->ridx2, &c->ecnt, &c->bbase, &c->xslot, &c->rkey32, &c->rkey32b, &c->bH, &c->bHs}) b->release();
     c->pkey16.release();
+    c->bcur.release();
     c->xsend.release();
     c->xH.release();
     c->xHs.release();
@@ -291,7 +304,7 @@ kmer_status kmer_close(kmer_ctx *c) {
     for (auto *b : {&c->gm_idx, &c->gm_idx2, &c->gm_head, &c->gm_gid, &c->gm_start}) b->release();
     c->gm_flag.release();
     dfree(c->d_ticket); dfree(c->d_bticket); dfree(c->d_scal); dfree(c->d_pos); dfree(c->d_pos_saved);
-    dfree(c->d_P); dfree(c->d_PR);
+    dfree(c->d_P); dfree(c->d_PR); dfree(c->d_stamp);
     if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->h_tail) (void)hipHostFree(c->h_tail);
     for (hipStream_t us : c->up_streams) (void)hipStreamSynchronize(us);

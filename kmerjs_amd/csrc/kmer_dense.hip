@@ -1,5 +1,5 @@
 // kmer_dense.hip — the dense-hit ordered path (a prefix of 0-3 bases, or none;
-// step 1, k <= 32): only the ACCEPTED windows are written, in rank order.
+// step 1, k <= 64): only the ACCEPTED windows are written, in rank order.
 //
 // lib/kmers.js:88-100 on a sequence line and on its complement (:151-155):
 // the Map's insertion order is line by line, the line's forward windows by

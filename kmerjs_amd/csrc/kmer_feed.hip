@@ -116,8 +116,18 @@ kmer_status wait_tail(kmer_ctx *c, uint64_t seq, hipStream_t qs) {
     return KMER_OK;
 }
 
+// The scan / feed times of the chunk whose tail was just read: its device
+// clock stamps came with the counters (no event on the chunk's stream).
+static void take_chunk_stamps(kmer_ctx *c) {
+    if (c->tmode != kmer_ctx::TIME_STAMPS) return;
+    const uint64_t t0 = c->h_tail[TAIL_STAMP + STAMP_SCAN_START], t1 = c->h_tail[TAIL_STAMP + STAMP_SCAN_END],
+                   t2 = c->h_tail[TAIL_STAMP + STAMP_FEED_END];
+    c->scan_ms += (double)(int64_t)(t1 - t0) / c->clock_khz;
+    c->feed_ms += (double)(int64_t)(t2 - t0) / c->clock_khz;
+}
+
 // Read the scan / feed kernel times of the last chunk (lazily: the chunk's
-// host wait returns before its closing event).
+// host wait returns before its closing event).  Event timing only.
 kmer_status resolve_feed_timing(kmer_ctx *c) {
     if (!c->feed_timing_pending) return KMER_OK;
     float ms = 0.f, ms_all = 0.f;
@@ -134,7 +144,8 @@ kmer_status resolve_feed_timing(kmer_ctx *c) {
 kmer_status flush_prep(kmer_ctx *c, hipStream_t s, uint32_t extra) {
     const uint32_t f = c->prep_flags | extra;
     if (!f) return KMER_OK;
-    HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, f, c->prep_lines, s));
+    HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, f, c->prep_lines,
+                          c->tmode == kmer_ctx::TIME_STAMPS ? c->d_stamp : nullptr, s));
     c->prep_flags = 0;
     return KMER_OK;
 }
@@ -147,6 +158,7 @@ kmer_status check_err(kmer_ctx *c, uint32_t e) {
                                               : "long-line mode: a line longer than 2^40 bytes or more than 2^23 lines");
     if (e & ERR_LOOKBACK_TIMEOUT) return fail(c, KMER_E_DEVICE, "tile look-back timed out");
     if (e & ERR_DENSE_RANK) return fail(c, KMER_E_DEVICE, "dense-hit path: rank slot past the counted hits");
+    if (e & ERR_BKT_RANK) return fail(c, KMER_E_DEVICE, "bucket finish: a partitioned rank past the hits");
     return KMER_OK;
 }
 
@@ -203,11 +215,16 @@ void bind_hits(kmer_ctx *c, HitArgs &h) {
 kmer_status launch_chunk(kmer_ctx *c) {
     auto &p = c->pend;
     const hipStream_t s = p.s;
-    HIPCHK(c, hipEventRecord(c->ev0, s));
+    // (phase times: clock stamps by the prologue, the tile reduce and the
+    // chunk tail -- the stream stood idle at every event record between two
+    // launches; KMERHIP_TIMING=events: as before, A/B experiments)
+    const bool events = c->tmode == kmer_ctx::TIME_EVENTS;
+    uint64_t *stamp = c->tmode == kmer_ctx::TIME_STAMPS ? c->d_stamp : nullptr;
+    if (events) HIPCHK(c, hipEventRecord(c->ev0, s));
     if (c->planes) HIPCHK(c, launch_scan_planes(p.a, c->pargs, s));
     else HIPCHK(c, launch_scan_tiles(p.a, s));
-    HIPCHK(c, hipEventRecord(c->ev1, s));
-    HIPCHK(c, launch_tile_reduce(c->tsum.p, p.n_tiles, c->bsum.p, s));
+    if (events) HIPCHK(c, hipEventRecord(c->ev1, s));
+    HIPCHK(c, launch_tile_reduce(c->tsum.p, p.n_tiles, c->bsum.p, stamp, s));
     if (p.n_blocks > TSCAN_INLINE_MAX) {
         TileSum zero;
         memset(&zero, 0, sizeof(zero));
@@ -217,10 +234,14 @@ kmer_status launch_chunk(kmer_ctx *c) {
         HIPCHK(c, launch_tile_scan(c->tsum.p, p.n_tiles, c->bsum.p, false, p.init, c->tscan.p, s));
     }
     p.h.seq = ++c->tail_seq;
-    HIPCHK(c, launch_hits(p.h, s));          // (+ the chunk tail: position, counters -> h_tail)
-    HIPCHK(c, hipEventRecord(c->ev4, s));
-    if (s != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev4, 0));   // later work follows the chunk
-    c->feed_timing_pending = true;
+    p.h.stamp = stamp;
+    HIPCHK(c, launch_hits(p.h, s));          // (+ the chunk tail: position, counters, stamps -> h_tail)
+    if (events) HIPCHK(c, hipEventRecord(c->ev4, s));
+    if (s != c->stream) {                        // later work follows the chunk
+        HIPCHK(c, hipEventRecord(c->evw, s));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
+    }
+    c->feed_timing_pending = events;
     return KMER_OK;
 }
 
@@ -348,6 +369,7 @@ kmer_status settle(kmer_ctx *c) {
     for (int attempt = 0;; ++attempt) {
         st = wait_tail(c, p.h.seq, s);
         if (st) return st;
+        take_chunk_stamps(c);
         const uint32_t e = (uint32_t)c->h_small[5];
         st = check_err(c, e);
         if (st) return st;
@@ -382,6 +404,8 @@ kmer_status settle(kmer_ctx *c) {
         }
         bind_hits(c, p.h);
         HIPCHK(c, hipMemsetAsync(c->d_scal, 0, 3 * 8, s));   // rec, ovf, cross counts of this chunk
+        if (c->tmode == kmer_ctx::TIME_STAMPS)               // (the redo's scan start)
+            HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, 0, 0, c->d_stamp, s));
         st = launch_chunk(c);
         if (st) return st;
     }
@@ -999,6 +1023,8 @@ kmer_status reset(kmer_ctx *c) {
     c->chunk_open = false;
     c->out_pending = false;
     c->timing_pending = false;
+    c->finish_stamped = false;
+    c->bkt_check = false;                        // (an unobserved finish: its ERR_BKT_CAP goes with it)
     c->n_out = 0;
     c->t_keys = 0;
     c->t_fill = 0;

@@ -15,7 +15,9 @@ kmer_status apply_cross(kmer_ctx *c) {
     if (n == 0) return KMER_OK;
     uint32_t *k32 = c->narrow ? c->rkey32.p : nullptr;
     if (!c->long_seg) {
-        HIPCHK(c, launch_cross_segsort(c->xord.p, c->xkey.p, c->xslot.p, n, c->rkey.p, k32, c->rord.p, c->pbits, s));
+        HIPCHK(c, launch_cross_segsort(c->xord.p, c->xkey.p, c->xslot.p, n, c->rkey.p, k32, c->rord.p, c->pbits,
+                                       c->fin_stamp, s));
+        c->fin_stamp = nullptr;                  // (the finish's first kernel has its start stamp)
     } else if (n <= XSMALL_MAX) {
         HIPCHK(c, launch_cross_sort_small(c->xslot.p, c->xord.p, c->xkey.p, n, c->rkey.p, k32, c->rord.p, s));
     } else {
@@ -84,9 +86,18 @@ kmer_status sort_and_heads_wide(kmer_ctx *c, uint64_t n) {
     return KMER_OK;
 }
 
-// bucket partition + per-bucket LDS tables (keys of <= BKT_LOW + 11 bits):
-// histogram per (bucket, block), offsets (one kernel), scatter, tables
-kmer_status bucket_heads(kmer_ctx *c, uint64_t n) {
+bool bucket_route(const kmer_ctx *c, bool with_counts) {
+    // (merged partials carry counts: the sort finish sums them in 64 bits)
+    return c->narrow && c->kbits <= BKT_LOW + 11 && !with_counts && !(c->p.flags & KMER_FLAG_SORT_FINISH);
+}
+
+// bucket partition + per-bucket LDS tables (keys of <= BKT_LOW + 11 bits).
+// One-pass route: every bucket has a fixed region of bucket_cap(n, nb)
+// entries and the blocks claim their runs in it (bucket_onepass_kernel); a
+// bucket that outgrows its region sets ERR_BKT_CAP, seen where the result is
+// first observed (bucket_observe), and the finish is redone on the counted
+// route: histogram per (bucket, block), offsets (one kernel), scatter.
+kmer_status bucket_heads(kmer_ctx *c, uint64_t n, bool partial) {
     hipStream_t s = c->stream;
     const uint32_t shift = std::min<uint32_t>(c->kbits, BKT_LOW);
     const uint32_t nb = 1u << (c->kbits - shift);
@@ -94,16 +105,35 @@ kmer_status bucket_heads(kmer_ctx *c, uint64_t n) {
     if (nblk64 > 0x7FFFFFFFull) return fail(c, KMER_E_BAD_PARAM, "too many hits");
     const uint32_t nblk = (uint32_t)nblk64;
     const uint32_t invalid = 1u << c->kbits;
+    uint64_t *stamp = c->fin_stamp;              // (non-null: this is the finish's first kernel)
+    c->fin_stamp = nullptr;
+    const uint64_t cap = bucket_cap(n, nb);
+    if (!c->bkt_counted && (uint64_t)nb * cap <= 0x7FFFFFFFull) {
+        HIPCHK(c, c->pkey16.ensure((uint64_t)nb * cap, s));
+        HIPCHK(c, c->ridx2.ensure((uint64_t)nb * cap, s));
+        if (!c->bcur.p) {                        // (once: bucket_heads_kernel leaves the cursors at 0)
+            HIPCHK(c, c->bcur.ensure((uint64_t)BKT_MAX * BKT_CUR_STRIDE, s));
+            HIPCHK(c, hipMemsetAsync(c->bcur.p, 0, (uint64_t)BKT_MAX * BKT_CUR_STRIDE * sizeof(uint32_t), s));
+        }
+        HIPCHK(c, launch_bucket_onepass(c->rkey32.p, n, invalid, shift, nb, nblk, (uint32_t)cap, c->bcur.p, c->pkey16.p,
+                                        c->ridx2.p, c->hcnt.p, c->d_err, stamp, s));
+        HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, nullptr, nb, shift, c->hcnt.p, c->bcur.p, (uint32_t)cap, n,
+                                      c->d_err, s));
+        c->bkt_check = true;
+        c->bkt_n = n;
+        c->bkt_partial = partial;
+        return KMER_OK;
+    }
     HIPCHK(c, c->bH.ensure((uint64_t)nb * nblk, s));
     HIPCHK(c, c->bHs.ensure((uint64_t)nb * nblk, s));
     HIPCHK(c, c->pkey16.ensure(n, s));
     HIPCHK(c, c->ridx2.ensure(n, s));
     HIPCHK(c, c->bbase.ensure(2 * BKT_MAX + 2, s));   // bucket totals [0, nb), starts [BKT_MAX, BKT_MAX + nb]
     uint32_t *btot = c->bbase.p, *bstart = c->bbase.p + BKT_MAX;
-    HIPCHK(c, launch_bucket_hist(c->rkey32.p, n, invalid, shift, nb, nblk, c->bH.p, c->hcnt.p, s));
+    HIPCHK(c, launch_bucket_hist(c->rkey32.p, n, invalid, shift, nb, nblk, c->bH.p, c->hcnt.p, stamp, s));
     HIPCHK(c, launch_bucket_offsets(c->bH.p, nb, nblk, c->bHs.p, btot, bstart, c->d_bticket, s));
     HIPCHK(c, launch_bucket_scatter(c->rkey32.p, n, invalid, shift, nb, nblk, c->bHs.p, bstart, c->pkey16.p, c->ridx2.p, s));
-    HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, bstart, nb, shift, c->hcnt.p, s));
+    HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, bstart, nb, shift, c->hcnt.p, nullptr, 0, n, c->d_err, s));
     return KMER_OK;
 }
 
@@ -145,20 +175,52 @@ kmer_status compact_windows(kmer_ctx *c) {
     return KMER_OK;
 }
 
+// After the stream has been synchronised behind a one-pass bucket finish:
+// the error word its emit sent along.  *redo: a bucket outgrew its region --
+// the context takes the counted route from here on and the caller redoes
+// rank_finish (the rank arrays are intact).
+static kmer_status bucket_observe(kmer_ctx *c, bool *redo) {
+    *redo = false;
+    if (!c->bkt_check) return KMER_OK;
+    c->bkt_check = false;
+    const uint32_t e = (uint32_t)c->h_tail[TAIL_ERR];
+    if (e & ERR_BKT_RANK) return check_err(c, e);
+    if (e & ERR_BKT_CAP) {
+        if (exp_env("KMERHIP_BKT_LOG")) fprintf(stderr, "bucket finish: a bucket past its region, counted route\n");
+        c->bkt_counted = true;
+        *redo = true;
+    }
+    return KMER_OK;
+}
+
 // resolve a deferred unique count (finish without a host result)
 kmer_status resolve_out(kmer_ctx *c) {
     kmer_status st = resolve_feed_timing(c);
     if (st) return st;
     if (c->out_pending) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->n_out = c->h_tail[8];
+        c->n_out = c->h_tail[TAIL_NUNIQ];
         c->out_pending = false;
+        bool redo = false;
+        st = bucket_observe(c, &redo);
+        if (st) return st;
+        if (redo) {                              // (the rank arrays are as the finish left them)
+            uint64_t nu = 0;
+            st = rank_finish(c, c->bkt_n, c->bkt_partial, false, &nu, true);
+            if (st) return st;
+            c->n_out = nu;
+        }
     }
     if (c->timing_pending) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventSynchronize(c->ev3));
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev2, c->ev3));
-        c->finish_ms = ms;
+        if (c->finish_stamped) {                 // (start: the finish's first kernel; end: the emit)
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->finish_ms = (double)(int64_t)(c->h_tail[TAIL_FIN_END] - c->h_tail[TAIL_FIN_START]) / c->clock_khz;
+        } else {
+            float ms = 0.f;
+            HIPCHK(c, hipEventSynchronize(c->ev3));
+            HIPCHK(c, hipEventElapsedTime(&ms, c->ev2, c->ev3));
+            c->finish_ms = ms;
+        }
         c->timing_pending = false;
     }
     return KMER_OK;
@@ -174,6 +236,7 @@ kmer_status resolve_out(kmer_ctx *c) {
 kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts, uint64_t *nu_out, bool sync) {
     hipStream_t s = c->stream;
     *nu_out = 0;
+    c->bkt_check = false;
     if (n == 0) return KMER_OK;
     if (c->narrow) HIPCHK(c, c->rkey32b.ensure(n, s));
     else HIPCHK(c, c->rkey2.ensure(n, s));
@@ -190,12 +253,11 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
     }
     const uint64_t invalid = c->kbits >= 63 ? ~0ull : (1ull << c->kbits);
     kmer_status st;
-    // (merged partials carry counts: the sort finish sums them in 64 bits)
-    const bool bucket = c->narrow && c->kbits <= BKT_LOW + 11 && !with_counts && !(c->p.flags & KMER_FLAG_SORT_FINISH);
+    const bool bucket = bucket_route(c, with_counts);
     if (c->wide)
         st = sort_and_heads_wide(c, n);          // (no partials / merged counts: refused for wide keys)
     else if (bucket)
-        st = bucket_heads(c, n);
+        st = bucket_heads(c, n, partial);
     else if (c->narrow)
         st = sort_and_heads<uint32_t>(c, c->rkey32.p, c->rkey32b.p, n, with_counts);
     else
@@ -224,7 +286,10 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
     e.n = n;
     e.invalid_key = invalid;
     e.nuniq = c->d_nuniq;
-    e.nuniq_host = c->d_tail + 8;
+    e.nuniq_host = c->d_tail + TAIL_NUNIQ;
+    e.host_out = c->d_tail;
+    e.err = c->d_err;
+    e.stamp = c->fin_emit;
     e.k = c->p.k;
     e.plen = (uint32_t)c->prefix.size();
     e.partial = partial ? 1u : 0u;
@@ -240,7 +305,11 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
         return KMER_OK;
     }
     HIPCHK(c, hipStreamSynchronize(s));
-    *nu_out = c->h_tail[8];
+    *nu_out = c->h_tail[TAIL_NUNIQ];
+    bool redo = false;
+    st = bucket_observe(c, &redo);
+    if (st) return st;
+    if (redo) return rank_finish(c, n, partial, with_counts, nu_out, true);   // (now on the counted route)
     return KMER_OK;
 }
 
@@ -496,7 +565,15 @@ kmer_status finish(kmer_ctx *c, kmer_result **out) {
     if (!c->open_stream) return fail(c, KMER_E_STATE, "finish without reset/feed");
     kmer_status st = settle(c);
     if (st) return st;
-    HIPCHK(c, hipEventRecord(c->ev2, c->stream));
+    // The packed path's bucket finish is timed by clock stamps: its first
+    // kernel (cross_segsort, or the partition) stamps the start, the emit the
+    // end, and nothing but launches touches the stream after the chunk's tail.
+    // Every other finish keeps its events.
+    const bool stamped = c->tmode == kmer_ctx::TIME_STAMPS && c->mode == MODE_PACKED && c->n_hits > 0 &&
+                         bucket_route(c, false) && !(c->n_cross && c->long_seg);
+    const bool events = !stamped && c->tmode != kmer_ctx::TIME_NONE;
+    c->fin_stamp = c->fin_emit = stamped ? c->d_stamp : nullptr;
+    if (events) HIPCHK(c, hipEventRecord(c->ev2, c->stream));
     uint64_t nu = 0;
     c->n_out = 0;
     const bool sync = out || c->p.max_keys;
@@ -508,6 +585,7 @@ kmer_status finish(kmer_ctx *c, kmer_result **out) {
             if (st) return st;
         }
         st = rank_finish(c, c->n_hits, false, false, &nu, sync);
+        c->fin_stamp = c->fin_emit = nullptr;
         if (st) return st;
         c->n_out = nu;
     } else if (c->mode == MODE_TABLE) {
@@ -517,8 +595,9 @@ kmer_status finish(kmer_ctx *c, kmer_result **out) {
         st = general_finish(c);
         if (st) return st;
     }
-    HIPCHK(c, hipEventRecord(c->ev3, c->stream));
-    c->timing_pending = true;
+    if (events) HIPCHK(c, hipEventRecord(c->ev3, c->stream));
+    c->timing_pending = stamped || events;
+    c->finish_stamped = stamped;
     c->open_stream = false;
     if (!sync) return KMER_OK;
     st = resolve_out(c);

@@ -171,6 +171,11 @@ struct kmer_ctx {
     DBuf<uint32_t> hcnt;           // by rank: != 0 iff first occurrence of its key (bucket finish: count)
     DBuf<uint32_t> bH, bHs;        // bucket finish: per (bucket, block) counts, their scan
     DBuf<uint16_t> pkey16;         // bucket finish: low key bits, partitioned
+    DBuf<uint32_t> bcur;           // one-pass partition: bucket cursors (BKT_CUR_STRIDE apart; 0 between finishes)
+    bool bkt_counted = false;      // a bucket outgrew its fixed region: the counted partition until the close
+    bool bkt_check = false;        // the last finish took the one-pass route, ERR_BKT_CAP not yet looked at
+    uint64_t bkt_n = 0;            // ... its hits and kind (the counted route redoes it from the rank arrays)
+    bool bkt_partial = false;
     DBuf<XHit> xsend;              // hit exchange: valid hits partitioned by owner rank
     DBuf<uint32_t> xH, xHs;        // ... per (owner, block) counts, their scan
     DBuf<uint64_t> xcnt;           // ... per owner totals (device)
@@ -213,7 +218,7 @@ struct kmer_ctx {
     bool open_stream = false;      // reset called, not finished
     std::unordered_map<std::string, Ent> exotic;
     uint64_t *h_small = nullptr;   // pinned (24 words): [0..7] copy of d_scal, [8..11] pos, [12..17] table feed
-    uint64_t *h_tail = nullptr;    // pinned, mapped, coherent: d_scal[0..7] written by the chunk tail kernel
+    uint64_t *h_tail = nullptr;    // pinned, mapped, coherent (TAIL_*): d_scal[0..7] written by the chunk tail kernel, ...
     // pinned staging of every host -> device upload (upload()): a pageable
     // hipMemcpyAsync may read its host buffer after the call returns, so the
     // bytes are copied here first; a region is reused only after the streams
@@ -286,7 +291,15 @@ struct kmer_ctx {
     double t_ms[7] = {};           // table phase times since the reset: lines, hist1, scatter1, hist2, scatter2, final, fasta
     hipEvent_t fa_ev[2] = {nullptr, nullptr};   // around a chunk's FASTA rewrite
     int n_cu = 0;
-    // timing (HIP events on the context stream)
+    // timing: the packed path's chunk and bucket finish by device clock stamps
+    // (no event between the launches of a step); every other path by HIP
+    // events on the context stream
+    enum { TIME_STAMPS, TIME_EVENTS, TIME_NONE } tmode = TIME_STAMPS;   // (experiments: KMERHIP_TIMING)
+    uint64_t *d_stamp = nullptr;   // STAMP_* words
+    double clock_khz = 0.0;        // rate of wall_clock64 (hipDeviceAttributeWallClockRate)
+    uint64_t *fin_stamp = nullptr; // finish(): handed to the first kernel of the finish (it stamps STAMP_FINISH_START)
+    uint64_t *fin_emit = nullptr;  // ... and to the emit (finish start / end -> h_tail)
+    bool finish_stamped = false;   // the pending finish time is in h_tail's stamps, not in ev2 / ev3
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, ev4 = nullptr;
     hipEvent_t evw = nullptr;      // cross-stream wait (no timing)
     double scan_ms = 0.0, feed_ms = 0.0, finish_ms = 0.0;
@@ -402,6 +415,7 @@ kmer_status ensure_records(kmer_ctx *c, uint64_t n);
 kmer_status drain_records(kmer_ctx *c, const uint8_t *d_data, uint64_t n, hipStream_t s);
 kmer_status wait_tail(kmer_ctx *c, uint64_t seq, hipStream_t qs);
 kmer_status resolve_feed_timing(kmer_ctx *c);
+bool bucket_route(const kmer_ctx *c, bool with_counts);
 kmer_status flush_prep(kmer_ctx *c, hipStream_t s, uint32_t extra);
 kmer_status check_err(kmer_ctx *c, uint32_t e);
 kmer_status ensure_rank_arrays(kmer_ctx *c, uint64_t need, uint64_t keep, hipStream_t s);
@@ -428,7 +442,7 @@ kmer_status feed(kmer_ctx *c, const uint8_t *d, uint64_t len, hipStream_t s);
 kmer_status reset(kmer_ctx *c);
 kmer_status apply_cross(kmer_ctx *c);
 kmer_status sort_and_heads_wide(kmer_ctx *c, uint64_t n);
-kmer_status bucket_heads(kmer_ctx *c, uint64_t n);
+kmer_status bucket_heads(kmer_ctx *c, uint64_t n, bool partial);
 kmer_status compact_windows(kmer_ctx *c);
 kmer_status resolve_out(kmer_ctx *c);
 kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts, uint64_t *nu_out, bool sync = true);

@@ -64,6 +64,8 @@ enum : uint32_t {
     ERR_TAB_SPLIT = 1u << 9,         // table mode: bucket range could not be split further
     ERR_DENSE_RANK = 1u << 10,       // dense-hit path: a rank slot past the counted hits (count / write disagree)
     ERR_TAB_CAP = 1u << 11,          // table mode: a bucket past its fixed pass-2 capacity (counted route redoes it)
+    ERR_BKT_CAP = 1u << 12,          // bucket finish: a run past its bucket's fixed region (counted route redoes it)
+    ERR_BKT_RANK = 1u << 13,         // bucket finish: a partitioned rank past the hits (a defect)
     // not an error: a tile without '\n' had hits, or a tile overflowed its hit
     // slots -- cross segments may be long (finish sorts the whole cross list)
     INFO_LONGSEG = 1u << 16,
@@ -213,7 +215,22 @@ struct HitArgs {
     unsigned long long *chunk_hits, *chunk_cross, *ends_open;
     uint64_t *host_out;            // mapped host memory: copy of scal[0..7], then [9] = seq
     uint64_t seq;                  // chunk sequence number (the host waits for it in host_out[9])
+    uint64_t *stamp;               // device clock stamps (STAMP_*): the tail writes FEED_END and copies
+                                   // [SCAN_START .. FEED_END] to host_out[TAIL_STAMP ..]; or null
 };
+
+// Device clock stamps (wall_clock64, a constant-rate counter) of the packed
+// path's phases: written by lane 0 of workgroup 0 of the kernels that delimit
+// them, so that no timing event sits between the launches of a step.
+enum : uint32_t { STAMP_SCAN_START = 0, STAMP_SCAN_END = 1, STAMP_FEED_END = 2, STAMP_FINISH_START = 3, STAMP_WORDS = 4 };
+// the mapped host words (kmer_ctx::h_tail): [0..7] device scalars, [8] unique
+// keys, [9] chunk sequence, [10] error word at the emit, [11..13] the chunk's
+// stamps, [14] finish start, [15] finish end
+enum : uint32_t { TAIL_NUNIQ = 8, TAIL_SEQ = 9, TAIL_ERR = 10, TAIL_STAMP = 11, TAIL_FIN_START = 14, TAIL_FIN_END = 15,
+                  TAIL_WORDS = 16 };
+__device__ __forceinline__ void stamp_now(uint64_t *stamp, uint32_t which) {
+    if (stamp && blockIdx.x == 0 && threadIdx.x == 0) stamp[which] = wall_clock64();
+}
 
 // By rank, after the key sort: the key and its total count if this rank is
 // the key's first occurrence, count 0 otherwise.
@@ -236,6 +253,9 @@ struct EmitArgs {
     uint64_t invalid_key;
     uint64_t *nuniq;
     uint64_t *nuniq_host;          // mapped host copy of *nuniq (or null)
+    uint64_t *host_out;            // mapped host words (TAIL_*): error word, finish stamps (or null)
+    const unsigned int *err;       // ... the device error word copied there
+    const uint64_t *stamp;         // ... the device stamps (STAMP_FINISH_START), or null
     uint32_t k, plen, partial;
     uint8_t P[KMAX_TILE];          // the prefix (|P| <= k <= 64 on the packed paths)
     uint8_t *keys_out;             // decode: n * k bytes
@@ -378,12 +398,12 @@ hipError_t launch_scan_tiles(const ScanArgs &a, hipStream_t s);
 hipError_t launch_scan_planes(const ScanArgs &a, const PlaneArgs &pa, hipStream_t s);
 hipError_t launch_hits(const HitArgs &a, hipStream_t s);
 // exclusive scan of the per-tile sums (init folded in); bsum / bscan: n_blocks scratch
-hipError_t launch_tile_reduce(const TileSum *in, uint32_t n, TileSum *bsum, hipStream_t s);
+hipError_t launch_tile_reduce(const TileSum *in, uint32_t n, TileSum *bsum, uint64_t *stamp, hipStream_t s);
 hipError_t launch_tile_scan(const TileSum *in, uint32_t n, const TileSum *bsum, bool bsum_scanned, TileSum init,
                             TileSum *out, hipStream_t s);
 enum : uint32_t { PREP_RESET = 1, PREP_SETPOS = 2, PREP_SAVE = 4, PREP_ZERO = 8 };
 hipError_t launch_prep(StreamPos *pos, StreamPos *saved, unsigned int *err, uint64_t *scal, uint32_t flags,
-                       uint64_t lines, hipStream_t s);
+                       uint64_t lines, uint64_t *stamp, hipStream_t s);
 hipError_t launch_tile_aggregate(const uint8_t *data, uint64_t len, uint32_t n_tiles, uint64_t *agg_cnt,
                                  uint64_t *agg_lnl, unsigned int *err, hipStream_t s);
 hipError_t launch_windows(const WindowArgs &a, uint32_t grid, hipStream_t s);
@@ -394,7 +414,7 @@ hipError_t launch_cross_sort_small(const uint32_t *slot, const uint64_t *ord, co
                                    uint64_t *rkey, uint32_t *rkey32, uint64_t *rord, hipStream_t s);
 constexpr uint64_t XSMALL_MAX = 16384;   // cross lists up to this size: one-workgroup sort
 hipError_t launch_cross_segsort(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t n, uint64_t *rkey,
-                                uint32_t *rkey32, uint64_t *rord, uint32_t pbits, hipStream_t s);
+                                uint32_t *rkey32, uint64_t *rord, uint32_t pbits, uint64_t *stamp, hipStream_t s);
 hipError_t launch_heads(const uint64_t *skey, const uint32_t *srank, uint64_t n, uint64_t invalid_key,
                         const uint64_t *rcnt, HeadRec *hrec, uint32_t *hcnt, hipStream_t s);
 // sort finish without per-entry counts: hcnt prefilled with 1, only groups of >= 2 and invalid keys written
@@ -425,15 +445,24 @@ hipError_t launch_heads_wide(const uint64_t *shi, const uint64_t *slo, const uin
 constexpr uint32_t BKT_LOW = 14;             // keys per bucket table: 2^14 (128 KiB of LDS: min rank, count)
 constexpr uint32_t BKT_MAX = 2048;           // buckets (keys of <= BKT_LOW + 11 bits)
 constexpr uint32_t BKT_EPB_HOST = 4096;      // elements per partition block (= BKT_EPB)
+constexpr uint32_t BKT_CUR_STRIDE = 32;      // one-pass partition: one bucket cursor per 128-byte line
+// the fixed region of a bucket on the one-pass route: 1.5 x the mean bucket
+// size + one block (a bucket past it sets ERR_BKT_CAP: the counted route redoes the finish)
+inline uint64_t bucket_cap(uint64_t n, uint32_t nb) { return (n + nb - 1) / nb * 3 / 2 + BKT_EPB_HOST; }
+hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
+                                 uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
+                                 uint32_t *hcnt, unsigned int *err, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_hist(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, hipStream_t s);
+                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_offsets(const uint32_t *H, uint32_t nb, uint32_t nblk, uint32_t *Hs, uint32_t *btot,
                                  uint32_t *bbase, unsigned int *ticket, hipStream_t s);
 hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
                                  uint32_t nblk, const uint32_t *Hs, const uint32_t *bbase, uint16_t *pkey,
                                  uint32_t *prank, hipStream_t s);
+// (cur != null: the one-pass route's regions of `cap` entries, totals in the cursors, which it returns to 0)
 hipError_t launch_bucket_heads(const uint16_t *pkey, const uint32_t *prank, const uint32_t *bbase, uint32_t nb,
-                               uint32_t shift, uint32_t *hcnt, hipStream_t s);
+                               uint32_t shift, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
+                               unsigned int *err, hipStream_t s);
 // multi-GPU hit exchange (kmer_exchange_prepare / kmer_finish_exchanged)
 struct XHit {
     uint64_t ord;                  // first-occurrence order key
@@ -677,10 +706,10 @@ hipError_t launch_tab_spill_fill(bool narrow, uint64_t *B1, uint64_t base, uint6
                                  const unsigned long long *pcur, hipStream_t s);
 hipError_t launch_tab_final(const TabFinal &a, uint32_t grid, hipStream_t s);
 hipError_t launch_tab_sort_final(const TabFinal &a, uint32_t grid, hipStream_t s);
-constexpr uint32_t TAB_SWG = 512;
+constexpr uint32_t TAB_SWG = 512;                       // sort-final workgroup (8 waves, two per CU)
 constexpr uint64_t TAB_SORT_KEYS = 12288;               // sort final: keys of a unit (one bucket, or narrow keys: TS_CAP1)
 constexpr uint64_t TAB_SORT_KEYS_BIG = 12160;           // ... with 16,384 bins (fixed regions: tab_sort_final_kernel<14>)
-constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a unit of several buckets (TS_CAPG)                      // sort-final workgroup (8 waves, two per CU)
+constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a unit of several buckets (TS_CAPG)
 hipError_t launch_tab_digest(const uint64_t *ent, const uint64_t *start, const uint32_t *nd, uint32_t k,
                             uint32_t narrow, unsigned long long *out,
                              hipStream_t s);

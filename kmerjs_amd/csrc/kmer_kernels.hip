@@ -1356,10 +1356,14 @@ __global__ __launch_bounds__(256) void hit_overflow_kernel(HitArgs a) {
     *a.chunk_hits = a.tscan[nt - 1].nh + a.tsum[nt - 1].nh;
     *a.chunk_cross = a.tscan[nt - 1].nx + a.tsum[nt - 1].nx;
     *a.ticket = 0;
+    if (a.stamp) a.stamp[STAMP_FEED_END] = wall_clock64();
     __threadfence();
     if (a.host_out) {
         for (int i = 0; i < 8; ++i)
             a.host_out[i] = __hip_atomic_load(a.scal + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (a.stamp)                             // (scan start, scan end, feed end: the chunk's phase times)
+            for (int i = 0; i <= (int)STAMP_FEED_END; ++i)
+                a.host_out[TAIL_STAMP + i] = __hip_atomic_load(a.stamp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence_system();
         __hip_atomic_store(a.host_out + 9, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -1415,7 +1419,9 @@ __device__ __forceinline__ TileSum ts_block_scan(TileSum v, TileSum *total) {
     return lane == 0 ? pre : tile_sum_op(pre, ex);
 }
 
-__global__ __launch_bounds__(256) void tile_reduce_kernel(const TileSum *in, uint32_t n, TileSum *bsum) {
+__global__ __launch_bounds__(256) void tile_reduce_kernel(const TileSum *in, uint32_t n, TileSum *bsum,
+                                                          uint64_t *stamp) {
+    stamp_now(stamp, STAMP_SCAN_END);            // (the first kernel after the scan)
     const uint32_t base = blockIdx.x * TSCAN_BLOCK;
     TileSum v = ts_zero();
 #pragma unroll
@@ -1463,7 +1469,7 @@ __global__ __launch_bounds__(256) void tile_scan_kernel(const TileSum *in, uint3
 // Feed prologue: the lazy reset / set_position of the host API, the position
 // snapshot for an overflow redo, the chunk's counters -- one launch.
 __global__ void prep_kernel(StreamPos *pos, StreamPos *saved, unsigned int *err, uint64_t *scal, uint32_t flags,
-                            uint64_t lines) {
+                            uint64_t lines, uint64_t *stamp) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     StreamPos p = *pos;
     if (flags & PREP_RESET) {
@@ -1477,6 +1483,7 @@ __global__ void prep_kernel(StreamPos *pos, StreamPos *saved, unsigned int *err,
     if (flags & (PREP_RESET | PREP_SETPOS)) *pos = p;
     if (flags & PREP_SAVE) *saved = p;
     if (flags & PREP_ZERO) scal[0] = scal[1] = scal[2] = 0;   // records, overflow hits, cross hits of the chunk
+    if (stamp) stamp[STAMP_SCAN_START] = wall_clock64();      // (the last kernel before the scan)
 }
 
 // Two-pass mode, pass 1: per-tile '\n' count and last '\n' position.
@@ -2572,7 +2579,8 @@ __global__ __launch_bounds__(1024) void cross_sort_small_kernel(const uint32_t *
 // then the scatter to the natural slots.
 __global__ __launch_bounds__(256) void cross_segsort_kernel(uint64_t *ord, uint64_t *key, const uint32_t *slot,
                                                             uint64_t n, uint64_t *rkey, uint32_t *rkey32,
-                                                            uint64_t *rord, uint32_t lsh) {
+                                                            uint64_t *rord, uint32_t lsh, uint64_t *stamp) {
+    stamp_now(stamp, STAMP_FINISH_START);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t line = ord[i] >> lsh;     // (the line bits of a segment never change while it is sorted)
         if (i > 0 && (ord[i - 1] >> lsh) == line) continue;
@@ -2724,7 +2732,8 @@ constexpr uint32_t BKT_EPB = 4096;           // elements per partition block
 
 __global__ __launch_bounds__(256) void bucket_hist_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
                                                           uint32_t shift, uint32_t nb, uint32_t nblk,
-                                                          uint32_t *H, uint32_t *hcnt) {
+                                                          uint32_t *H, uint32_t *hcnt, uint64_t *stamp) {
+    stamp_now(stamp, STAMP_FINISH_START);
     __shared__ uint32_t hist[BKT_MAX];
     for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[b] = 0;
     __syncthreads();
@@ -2920,17 +2929,137 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key
     }
 }
 
+constexpr uint32_t BKT_SKIP = 0x80000000u;   // one-pass partition: a run that did not fit its bucket's region
+
+// One-pass partition (fixed regions): the work of bucket_hist, bucket_offsets
+// and bucket_scatter in one launch.  bucket_heads_kernel applies only
+// atomicMin / atomicAdd per key, so the order of a bucket's entries does not
+// matter and a block needs no exact offset, only a run of its own inside the
+// bucket's region [b * cap, (b + 1) * cap): it groups its keys by bucket in
+// LDS (as bucket_scatter_kernel) and claims each non-empty bucket's run with
+// one returning atomicAdd on the bucket's cursor, all of a thread's claims
+// issued together (one round trip per block).  The cursors end as the bucket
+// totals (bucket_heads_kernel reads them and returns them to 0).  A run that
+// would end past the region is not written: ERR_BKT_CAP, and the host redoes
+// the finish with the counted kernels.  nb * cap < 2^31 (launcher).
+__global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
+                                                             uint32_t shift, uint32_t nb, uint32_t cap, uint32_t *cur,
+                                                             uint16_t *pkey, uint32_t *prank, uint32_t *hcnt,
+                                                             unsigned int *err, uint64_t *stamp) {
+    stamp_now(stamp, STAMP_FINISH_START);
+    __shared__ uint32_t cnt[BKT_MAX];          // per bucket: count, then local start, then global position
+    __shared__ uint32_t skey[BKT_EPB];
+    __shared__ uint32_t srank[BKT_EPB];
+    __shared__ uint32_t wtot[4];
+    for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * BKT_EPB;
+    // clear the head counts of this block's ranks (bucket_heads sets the heads')
+    for (uint32_t j = 4 * threadIdx.x; j < BKT_EPB; j += 4 * 256) {
+        const uint64_t i = base + j;
+        if (i + 4 <= n) *(uint4 *)(hcnt + i) = make_uint4(0, 0, 0, 0);
+        else for (uint64_t t = i; t < n; ++t) hcnt[t] = 0;
+    }
+    uint32_t kk[BKT_EPB / 256], li[BKT_EPB / 256];
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
+        const uint64_t i = base + u * 256 + threadIdx.x;
+        kk[u] = i < n ? key[i] : invalid;
+        li[u] = kk[u] != invalid ? atomicAdd(&cnt[kk[u] >> shift], 1u) : 0u;
+    }
+    __syncthreads();
+    // exclusive scan of the bucket counts (nb <= BKT_MAX, <= 8 per thread)
+    uint32_t loc[BKT_MAX / 256], sum = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
+        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+        loc[u] = b < nb ? cnt[b] : 0u;
+        sum += loc[u];
+    }
+    // the claims: this block's run of each owned bucket, region-relative; in
+    // flight during the scan and the placement
+    uint32_t gpos[BKT_MAX / 256];
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
+        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+        gpos[u] = b < nb && loc[u] ? atomicAdd(cur + (uint64_t)b * BKT_CUR_STRIDE, loc[u]) : 0u;
+    }
+    const uint32_t incl = wave_incl_sum(sum);
+    if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint32_t pre = incl - sum;
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) pre += wtot[w];
+    uint32_t lst[BKT_MAX / 256];
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
+        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+        lst[u] = pre;                            // local start of bucket b in skey / srank
+        if (b < nb) cnt[b] = pre;
+        pre += loc[u];
+    }
+    const uint32_t valid = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
+        if (kk[u] != invalid) {
+            const uint32_t p = cnt[kk[u] >> shift] + li[u];
+            skey[p] = kk[u];
+            srank[p] = (uint32_t)(base + u * 256 + threadIdx.x);
+        }
+    }
+    // every wave has read its local starts before cnt[] is rewritten (the
+    // race fixed in bucket_scatter_kernel)
+    __syncthreads();
+    // cnt[b] := global position of local element 0 of bucket b (mod 2^32:
+    // element e of bucket b goes to cnt[b] + e), or BKT_SKIP
+    bool over = false;
+#pragma unroll
+    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
+        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+        if (b < nb && loc[u]) {
+            const bool fits = (uint64_t)gpos[u] + loc[u] <= cap;
+            cnt[b] = fits ? b * cap + gpos[u] - lst[u] : BKT_SKIP;
+            over |= !fits;
+        }
+    }
+    if (over) atomicOr(err, ERR_BKT_CAP);
+    __syncthreads();
+    const uint32_t lo_mask = (1u << shift) - 1u;
+    for (uint32_t e = threadIdx.x; e < valid; e += 256) {
+        const uint32_t k = skey[e], b = k >> shift;
+        const uint32_t c = cnt[b];
+        if (c == BKT_SKIP) continue;
+        const uint32_t pos = c + e;              // (< (b + 1) * cap <= nb * cap: inside pkey / prank)
+        pkey[pos] = (uint16_t)(k & lo_mask);
+        prank[pos] = srank[e];
+    }
+}
+
+// (cur: the one-pass route -- bucket b's entries are [b * cap, b * cap +
+// total), the total read from the bucket's cursor, which goes back to 0 for
+// the next finish; a bucket past its region is skipped: its finish is redone)
 __global__ __launch_bounds__(1024) void bucket_heads_kernel(const uint16_t *pkey, const uint32_t *prank,
-                                                            const uint32_t *bbase, uint32_t shift, uint32_t *hcnt) {
+                                                            const uint32_t *bbase, uint32_t shift, uint32_t *hcnt,
+                                                            uint32_t *cur, uint32_t cap, uint64_t n,
+                                                            unsigned int *err) {
     __shared__ uint32_t minr[1u << BKT_LOW];
     __shared__ uint32_t cnt[1u << BKT_LOW];
+    __shared__ uint32_t s_tot;
     const uint32_t b = blockIdx.x, nk = 1u << shift;
+    if (cur && threadIdx.x == 0) s_tot = atomicExch(cur + (uint64_t)b * BKT_CUR_STRIDE, 0u);
     for (uint32_t j = threadIdx.x; j < nk; j += blockDim.x) {
         minr[j] = 0xFFFFFFFFu;
         cnt[j] = 0;
     }
     __syncthreads();
-    const uint32_t lo = bbase[b], hi = bbase[b + 1];
+    uint32_t lo, hi;
+    if (cur) {
+        lo = b * cap;
+        hi = s_tot <= cap ? lo + s_tot : lo;
+    } else {
+        lo = bbase[b];
+        hi = bbase[b + 1];
+    }
     // 16 keys per thread loaded before any is used: one memory round trip per
     // 16 K keys, not one per 1 K (the loop waited on every load, ~10 per bucket)
     constexpr uint32_t U = 16;
@@ -2939,7 +3068,7 @@ __global__ __launch_bounds__(1024) void bucket_heads_kernel(const uint16_t *pkey
 #pragma unroll
         for (uint32_t u = 0; u < U; ++u) {
             const uint32_t e = e0 + u * 1024 + threadIdx.x;
-            j[u] = e < hi ? pkey[e] : 0u;
+            j[u] = e < hi ? pkey[e] & (nk - 1u) : 0u;   // (the mask: the table index never depends on the data)
             r[u] = e < hi ? prank[e] : 0u;
         }
 #pragma unroll
@@ -2953,7 +3082,11 @@ __global__ __launch_bounds__(1024) void bucket_heads_kernel(const uint16_t *pkey
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < nk; j += blockDim.x) {
         const uint32_t c = cnt[j];
-        if (c) hcnt[minr[j]] = c;       // (the key is rkey32 at that rank)
+        if (c) {
+            const uint32_t r = minr[j];
+            if (r < n) hcnt[r] = c;     // (the key is rkey32 at that rank)
+            else atomicOr(err, ERR_BKT_RANK);
+        }
     }
 }
 
@@ -3054,6 +3187,10 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
         const uint64_t oend = o0 + rt;
         if (r == n - 1) {
             *a.nuniq = o64 + f;
+            if (a.host_out) {                    // (the error word and the finish's start travel with the count)
+                a.host_out[TAIL_ERR] = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (a.stamp) a.host_out[TAIL_FIN_START] = a.stamp[STAMP_FINISH_START];
+            }
             if (a.nuniq_host) {
                 *a.nuniq_host = o64 + f;
                 __threadfence_system();
@@ -3127,6 +3264,11 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
             __syncthreads();                     // kbuf is reused by the next round
         }
         o0 = oend;
+    }
+    // the finish's end: the exit of the workgroup that wrote the unique count
+    if (a.host_out && a.stamp && blockIdx.x == gridDim.x - 1 && tid == 0) {
+        a.host_out[TAIL_FIN_END] = wall_clock64();
+        __threadfence_system();
     }
 }
 
@@ -3411,8 +3553,9 @@ hipError_t launch_hits(const HitArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_tile_reduce(const TileSum *in, uint32_t n, TileSum *bsum, hipStream_t s) {
-    hipLaunchKernelGGL(tile_reduce_kernel, dim3((n + TSCAN_BLOCK - 1) / TSCAN_BLOCK), dim3(256), 0, s, in, n, bsum);
+hipError_t launch_tile_reduce(const TileSum *in, uint32_t n, TileSum *bsum, uint64_t *stamp, hipStream_t s) {
+    hipLaunchKernelGGL(tile_reduce_kernel, dim3((n + TSCAN_BLOCK - 1) / TSCAN_BLOCK), dim3(256), 0, s, in, n, bsum,
+                       stamp);
     return hipGetLastError();
 }
 hipError_t launch_tile_scan(const TileSum *in, uint32_t n, const TileSum *bsum, bool bsum_scanned, TileSum init,
@@ -3422,8 +3565,8 @@ hipError_t launch_tile_scan(const TileSum *in, uint32_t n, const TileSum *bsum, 
     return hipGetLastError();
 }
 hipError_t launch_prep(StreamPos *pos, StreamPos *saved, unsigned int *err, uint64_t *scal, uint32_t flags,
-                       uint64_t lines, hipStream_t s) {
-    hipLaunchKernelGGL(prep_kernel, dim3(1), dim3(64), 0, s, pos, saved, err, scal, flags, lines);
+                       uint64_t lines, uint64_t *stamp, hipStream_t s) {
+    hipLaunchKernelGGL(prep_kernel, dim3(1), dim3(64), 0, s, pos, saved, err, scal, flags, lines, stamp);
     return hipGetLastError();
 }
 hipError_t launch_tile_aggregate(const uint8_t *data, uint64_t len, uint32_t n_tiles, uint64_t *agg_cnt,
@@ -3517,9 +3660,9 @@ hipError_t launch_cross_sort_small(const uint32_t *slot, const uint64_t *ord, co
     return hipGetLastError();
 }
 hipError_t launch_cross_segsort(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t n, uint64_t *rkey,
-                                uint32_t *rkey32, uint64_t *rord, uint32_t pbits, hipStream_t s) {
+                                uint32_t *rkey32, uint64_t *rord, uint32_t pbits, uint64_t *stamp, hipStream_t s) {
     if (n) hipLaunchKernelGGL(cross_segsort_kernel, dim3(grid_for(n)), dim3(256), 0, s, ord, key, slot, n, rkey, rkey32,
-                              rord, pbits + 1);
+                              rord, pbits + 1, stamp);
     return hipGetLastError();
 }
 // ---------------------------------------------------------------------------
@@ -3651,8 +3794,9 @@ hipError_t launch_heads32(const uint32_t *skey, const uint32_t *srank, uint64_t 
     return hipGetLastError();
 }
 hipError_t launch_bucket_hist(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, hipStream_t s) {
-    hipLaunchKernelGGL(bucket_hist_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, nblk, H, hcnt);
+                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, uint64_t *stamp, hipStream_t s) {
+    hipLaunchKernelGGL(bucket_hist_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, nblk, H, hcnt,
+                       stamp);
     return hipGetLastError();
 }
 hipError_t launch_bucket_offsets(const uint32_t *H, uint32_t nb, uint32_t nblk, uint32_t *Hs, uint32_t *btot,
@@ -3667,9 +3811,20 @@ hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t inval
                        pkey, prank);
     return hipGetLastError();
 }
+hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
+                                 uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
+                                 uint32_t *hcnt, unsigned int *err, uint64_t *stamp, hipStream_t s) {
+    // (region addresses are 32-bit, and BKT_SKIP must not be one of them)
+    if (nb == 0 || nb > BKT_MAX || (uint64_t)nb * cap > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bucket_onepass_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, cap, cur, pkey,
+                       prank, hcnt, err, stamp);
+    return hipGetLastError();
+}
 hipError_t launch_bucket_heads(const uint16_t *pkey, const uint32_t *prank, const uint32_t *bbase, uint32_t nb,
-                               uint32_t shift, uint32_t *hcnt, hipStream_t s) {
-    hipLaunchKernelGGL(bucket_heads_kernel, dim3(nb), dim3(1024), 0, s, pkey, prank, bbase, shift, hcnt);
+                               uint32_t shift, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
+                               unsigned int *err, hipStream_t s) {
+    hipLaunchKernelGGL(bucket_heads_kernel, dim3(nb), dim3(1024), 0, s, pkey, prank, bbase, shift, hcnt, cur, cap, n,
+                       err);
     return hipGetLastError();
 }
 uint64_t emit_blocks(uint64_t n) { return (n + EMIT_RPB - 1) / EMIT_RPB; }

@@ -17,6 +17,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+# the probed kernel is on the counted route (the probe builds read the switch; the shipping build does not)
+os.environ.setdefault("KMERHIP_BKT_ROUTE", "counted")
 
 from kmerjs_amd import _native  # noqa: E402
 from oracle import oracle  # noqa: E402
