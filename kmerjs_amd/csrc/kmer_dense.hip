@@ -25,27 +25,13 @@
 // complement of the bases in reverse order is the LS stream's bitwise not).
 // Non-ACGT bytes are flagged per byte (v_perm against "ACGT"); such windows
 // are not ranked but become records when their prefix bytes match.
-#include "kmer_internal.hpp"
+#include "kmer_device.hpp"
 
 namespace kmerhip {
 
 namespace {
 
 constexpr int DW_NS = 16;              // windows per lane per round
-
-__device__ __forceinline__ uint32_t dw_incl_sum(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return x;
-}
-
-__device__ __forceinline__ uint32_t rl32(uint32_t v, uint32_t i) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
-}
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
     return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src) |
@@ -102,22 +88,6 @@ __device__ __forceinline__ void dw_fetch(const DenseArgs &a, DCur &c) {
             c.dcnt = a.cnt[mi];
             c.dbase = a.hbase[mi];
         }
-    }
-}
-
-// exotic window (a byte outside A/C/G/T): its strands whose prefix bytes match
-// become records (their keys are gathered later), as the tile paths do
-__device__ __forceinline__ void dw_record(const DenseArgs &a, uint64_t order, uint64_t pos, uint32_t strand) {
-    const unsigned long long n = atomicAdd(a.rec_count, 1ull);
-    if (n < a.rec_cap) {
-        Record r;
-        r.order = order;
-        r.pos = pos;
-        r.len = a.k;
-        r.strand = strand;
-        a.recs[n] = r;
-    } else {
-        atomicOr(a.err, ERR_REC_OVERFLOW);
     }
 }
 
@@ -178,11 +148,11 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
         const uint64_t seg0 = c.seg;
         const uint64_t rem = lane == 0 ? (Wi > seg0 ? Wi - seg0 : 0) : Wi;
         const uint32_t need = lane < 16 ? (uint32_t)((rem + DW_NS - 1) / DW_NS) : 0u;
-        const uint32_t cum = dw_incl_sum(need);
-        const uint32_t tot = rl32(cum, 15);
+        const uint32_t cum = wave_incl_sum(need);
+        const uint32_t tot = readlane32(cum, 15);
         uint32_t li = 0;
 #pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) li += rl32(cum, i) <= lane ? 1u : 0u;
+        for (uint32_t i = 0; i < 16; ++i) li += readlane32(cum, i) <= lane ? 1u : 0u;
         const bool act = lane < tot && li < 16;
         const uint32_t lsrc = li < 16 ? li : 15u;
         const uint32_t before = (uint32_t)__shfl((int)(cum - need), (int)lsrc);
@@ -199,8 +169,8 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
         uint32_t is = 15, ci = 0;
         bool part = false;
         if (tot > 64) {
-            is = rl32(li, 63);
-            ci = rl32(cum, is);
+            is = readlane32(li, 63);
+            ci = readlane32(cum, is);
             part = ci != 64;
         }
         // ---- the lane's 16 windows: codes of the bytes [st + w0, st + w0 + 16 + k - 1) ----
@@ -283,9 +253,13 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
                     bf = bf && a.data[pos + b] == a.P[b];
                     br = br && a.data[pos + k - plen + b] == a.RP[b];
                 }
+                // exotic window (a byte outside A/C/G/T): its strands whose prefix bytes
+                // match become records (their keys are gathered later), as the tile paths do
                 const uint64_t s = w0 + m, lo = lix << (a.pbits + 1);
-                if (bf) dw_record(a, lo | s, pos, 0);
-                if (br) dw_record(a, lo | (1ull << a.pbits) | (maxrel - s), pos, 1);
+                if (bf) append_record(a.recs, a.rec_count, a.rec_cap, a.err, lo | s, pos, a.k, 0);
+                if (br)
+                    append_record(a.recs, a.rec_count, a.rec_cap, a.err, lo | (1ull << a.pbits) | (maxrel - s), pos, a.k,
+                                  1);
             }
         } else if (nv) {
             const uint8_t *p = a.data + st + w0;
@@ -344,8 +318,10 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
                             br = br && a.data[pos + k - plen + b] == a.RP[b];
                         }
                         const uint64_t s = w0 + m, lo = lix << (a.pbits + 1);
-                        if (bf) dw_record(a, lo | s, pos, 0);
-                        if (br) dw_record(a, lo | (1ull << a.pbits) | (maxrel - s), pos, 1);
+                        if (bf) append_record(a.recs, a.rec_count, a.rec_cap, a.err, lo | s, pos, a.k, 0);
+                        if (br)
+                            append_record(a.recs, a.rec_count, a.rec_cap, a.err, lo | (1ull << a.pbits) | (maxrel - s), pos, a.k,
+                                          1);
                     }
                     continue;
                 }
@@ -355,7 +331,7 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
         }
         // ---- ranks inside each line: segmented wave scans of the lane counts ----
         const uint32_t nf = __popc(fmask), nr = __popc(rmask);
-        const uint32_t F = dw_incl_sum(nf), Rs = dw_incl_sum(nr);
+        const uint32_t F = wave_incl_sum(nf), Rs = wave_incl_sum(nr);
         // carried counts of line m (seg0 > 0: earlier rounds took its first windows)
         const uint32_t carf = seg0 ? c.cf : 0u, carr = seg0 ? c.cr : 0u;
         // lane i < 16: line i's windows of this round = lanes [b_i, min(cum_i, 64))
@@ -434,8 +410,8 @@ __global__ __launch_bounds__(256) void dense_windows_kernel(DenseArgs a) {
             c.seg = 0;
             c.cf = c.cr = 0;
         } else {
-            const uint32_t bis = ci - rl32(need, is);
-            const uint32_t cfi = rl32(sf, is), cri = rl32(sr, is);
+            const uint32_t bis = ci - readlane32(need, is);
+            const uint32_t cfi = readlane32(sf, is), cri = readlane32(sr, is);
             c.cf = (is == 0 ? carf : 0u) + cfi;
             c.cr = (is == 0 ? carr : 0u) + cri;
             c.seg = (is == 0 ? seg0 : 0) + (uint64_t)(64 - bis) * DW_NS;

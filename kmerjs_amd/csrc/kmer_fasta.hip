@@ -30,7 +30,7 @@
 // Whether a line is a header depends on its first byte, which may lie in an
 // earlier tile: each tile (and each thread inside a tile) is a function of
 // the incoming state h (FaFn), composed by an exclusive scan.
-#include "kmer_internal.hpp"
+#include "kmer_device.hpp"
 
 namespace kmerhip {
 
@@ -156,22 +156,7 @@ __device__ __forceinline__ void fa_stage(const uint8_t *data, uint64_t len, int6
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t g = g0 + 16 * (tid + TPB * i);
-        uint4 v;
-        if (g + 16 <= (int64_t)len) {
-            v = *(const uint4 *)(data + g);
-        } else {
-            uint32_t w[4];
-            for (int q = 0; q < 4; ++q) {
-                uint32_t x = 0;
-                for (int b = 0; b < 4; ++b) {
-                    const int64_t p = g + 4 * q + b;
-                    x |= (uint32_t)((uint64_t)p < len ? data[p] : (uint8_t)'\n') << (8 * b);
-                }
-                w[q] = x;
-            }
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        *(uint4 *)(buf + 16 * (tid + TPB * i)) = v;
+        *(uint4 *)(buf + 16 * (tid + TPB * i)) = load_chunk(data, g, len);
     }
     if (tid == 0) buf[-1] = g0 > 0 ? data[g0 - 1] : (uint8_t)'\n';
     if (tid == 1) buf[FA_TILE] = (uint64_t)(g0 + FA_TILE) < len ? data[g0 + FA_TILE] : (uint8_t)'\n';

@@ -1,5 +1,6 @@
-// kmer_internal.hpp — shared definitions between the gfx950 kernels
-// (kmer_kernels.hip) and the host orchestration (kmer_api.hip).
+// kmer_internal.hpp — shared definitions between the gfx950 kernels (the
+// kmer_*.hip kernel files; their common device helpers are in kmer_device.hpp)
+// and the host orchestration (kmer_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -430,7 +431,6 @@ constexpr uint64_t EMIT_DIRECT_MAX = 4096;   // emit workgroups that sum the ear
 // entries' keys after apply_cross; heads over (hi, lo) sorted ranks (hcnt
 // prefilled with 1, as launch_heads_sparse)
 hipError_t launch_gather_u64(const uint64_t *src, const uint32_t *idx, uint64_t n, uint64_t *dst, hipStream_t s);
-hipError_t launch_gather_u32(const uint32_t *src, const uint32_t *idx, uint64_t n, uint32_t *dst, hipStream_t s);
 constexpr uint64_t CP_BLOCK = 4096;   // ranks per compaction workgroup (compact_count / compact_write)
 hipError_t launch_compact_count(const uint32_t *k32, const uint64_t *k64, uint64_t n, uint64_t invalid, uint32_t *bcnt,
                                 hipStream_t s);
@@ -706,7 +706,8 @@ hipError_t launch_tab_spill_fill(bool narrow, uint64_t *B1, uint64_t base, uint6
                                  const unsigned long long *pcur, hipStream_t s);
 hipError_t launch_tab_final(const TabFinal &a, uint32_t grid, hipStream_t s);
 hipError_t launch_tab_sort_final(const TabFinal &a, uint32_t grid, hipStream_t s);
-constexpr uint32_t TAB_SWG = 512;                       // sort-final workgroup (8 waves, two per CU)
+// sort-final workgroup (8 waves, two per CU)
+constexpr uint32_t TAB_SWG = 512;
 constexpr uint64_t TAB_SORT_KEYS = 12288;               // sort final: keys of a unit (one bucket, or narrow keys: TS_CAP1)
 constexpr uint64_t TAB_SORT_KEYS_BIG = 12160;           // ... with 16,384 bins (fixed regions: tab_sort_final_kernel<14>)
 constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a unit of several buckets (TS_CAPG)

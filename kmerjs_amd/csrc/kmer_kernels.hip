@@ -24,7 +24,7 @@
 // reverse-complement strand's window at j is rc of the forward window at
 // p = L-k-j, so both strands are served by ONE forward scan: a forward window
 // w at p yields key w if w starts with P, and key rc(w) if w ends with rc(P).
-#include "kmer_internal.hpp"
+#include "kmer_device.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -44,18 +44,6 @@ __device__ __forceinline__ void set_info(unsigned int *err, unsigned int bit) {
     if (!(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(err, bit);
 }
 
-// Inclusive wave64 prefix sum with DPP (row_shr 1/2/4/8 inside rows of 16,
-// then row_bcast 15 / 31 across rows): no LDS round trips on the critical path.
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return x;
-}
-
 // '\n' bytes among four ASCII bytes (< 0x80): bit 7 of (x ^ "\n\n\n\n") +
 // 0x7F per byte is set iff the byte is NOT '\n' (no carries: every byte < 0x80),
 // so the count is 4 - popcount.  One v_xad_u32 + and + bcnt per word.
@@ -71,13 +59,6 @@ __device__ __forceinline__ uint32_t not_nl_bits_xad(uint32_t x, uint32_t k0a, ui
     asm("v_xad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(k0a), "s"(k7f));
     return r & 0x80808080u;
 }
-
-// per-byte 0x80 flag for bytes equal to '\n'; exact for ASCII bytes (< 0x80)
-__device__ __forceinline__ uint32_t nl_flags(uint32_t x) {
-    uint32_t t = x ^ 0x0A0A0A0Au;
-    return ~(t + 0x7F7F7F7Fu) & 0x80808080u;
-}
-
 
 __device__ __forceinline__ uint8_t comp_byte(uint8_t c) {
     return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'G' ? 'C' : c == 'C' ? 'G' : c;
@@ -141,33 +122,6 @@ __device__ uint64_t look_back(unsigned long long *words, uint32_t tile, unsigned
 // ---------------------------------------------------------------------------
 // tile kernel
 // ---------------------------------------------------------------------------
-constexpr int NCH_MAIN = TILE / 16;          // 1024 16-byte chunks
-constexpr int NCH_FRONT = FH / 16;           // 4
-constexpr int NCH_BACK = BH / 16;            // 5
-constexpr int BUFSZ = FH + TILE + BH;
-
-// bytes outside [0, len) read as '\n' (a line boundary that is never a window byte)
-__device__ __noinline__ uint4 load_chunk_edge(const uint8_t *data, int64_t g, uint64_t len) {
-    uint32_t w[4];
-#pragma unroll 1
-    for (int i = 0; i < 4; ++i) {
-        uint32_t x = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int64_t p = g + i * 4 + b;
-            const uint32_t c = (p >= 0 && (uint64_t)p < len) ? data[p] : (uint32_t)'\n';
-            x |= c << (8 * b);
-        }
-        w[i] = x;
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__device__ __forceinline__ uint4 load_chunk(const uint8_t *data, int64_t g, uint64_t len) {
-    if (g >= 0 && (uint64_t)g + 16 <= len) return *(const uint4 *)(data + g);
-    return load_chunk_edge(data, g, len);
-}
-
-
 struct TileShared {
     uint32_t tpre[TPB + 1];      // exclusive '\n' count per thread inside the tile; [TPB] = total
     uint32_t wsum[TPB / 64];
@@ -228,34 +182,13 @@ __device__ __forceinline__ void revcomp_code128(uint64_t hi, uint64_t lo, uint32
 __device__ __forceinline__ uint32_t tile_prologue(const uint8_t *data, uint64_t len, int64_t g0, uint8_t *buf,
                                                   TileShared &sh, uint32_t (&w)[17], unsigned int *err) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    // ---- stage tile + halos into LDS (16 B per lane, coalesced) ----
-    uint4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = load_chunk(data, g0 + (int64_t)(tid + TPB * i) * 16, len);
-    uint4 vh = make_uint4(0, 0, 0, 0);
-    const bool halo = tid < NCH_FRONT + NCH_BACK;
-    const int hc = tid < NCH_FRONT ? tid : NCH_FRONT + NCH_MAIN + (tid - NCH_FRONT);
-    if (halo) vh = load_chunk(data, g0 - FH + (int64_t)hc * 16, len);
-    uint32_t orall = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        orall |= v[i].x | v[i].y | v[i].z | v[i].w;
-        *(uint4 *)(buf + FH + (tid + TPB * i) * 16) = v[i];
-    }
-    if (halo) *(uint4 *)(buf + hc * 16) = vh;
-    if (orall & 0x80808080u) atomicOr(err, ERR_NONASCII);
+    TileRegs r;
+    load_tile(data, len, g0, r);
+    if (store_tile(r, buf) & 0x80808080u) atomicOr(err, ERR_NONASCII);
     __syncthreads();
 
     // ---- per-thread view: bytes [64*tid, 64*tid + 68) ----
-    {
-        const uint4 *lp = (const uint4 *)(buf + FH + 64 * tid);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 x = lp[i];
-            w[4 * i] = x.x; w[4 * i + 1] = x.y; w[4 * i + 2] = x.z; w[4 * i + 3] = x.w;
-        }
-        w[16] = *(const uint32_t *)(buf + FH + 64 * tid + 64);
-    }
+    load_thread_words(buf + FH + 64 * tid, w);
     // ---- '\n' count of the bytes this thread owns (only real bytes < len) ----
     uint32_t cnt = 0;
     const int64_t gt = g0 + 64 * tid;
@@ -264,12 +197,7 @@ __device__ __forceinline__ uint32_t tile_prologue(const uint8_t *data, uint64_t 
         for (int i = 0; i < 16; ++i) cnt += __popc(nl_flags(w[i]));
     } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int64_t n = (int64_t)len - (gt + 4 * i);
-            uint32_t z = nl_flags(w[i]);
-            if (n <= 0) z = 0; else if (n < 4) z &= (1u << (8 * n)) - 1u;
-            cnt += __popc(z);
-        }
+        for (int i = 0; i < 16; ++i) cnt += __popc(nl_flags_below(w[i], (int64_t)len - (gt + 4 * i)));
     }
     // ---- block exclusive scan of cnt ----
     uint32_t incl = cnt;
@@ -294,9 +222,8 @@ __device__ __forceinline__ uint32_t tile_prologue(const uint8_t *data, uint64_t 
         int lastpos = -1;
 #pragma unroll 1
         for (int i = 15; i >= 0 && lastpos < 0; --i) {
-            const int64_t n = (int64_t)len - (gt + 4 * i);
-            uint32_t z = nl_flags(*(const uint32_t *)(buf + FH + 64 * tid + 4 * i));
-            if (n <= 0) z = 0; else if (n < 4) z &= (1u << (8 * n)) - 1u;
+            const uint32_t z = nl_flags_below(*(const uint32_t *)(buf + FH + 64 * tid + 4 * i),
+                                              (int64_t)len - (gt + 4 * i));
             if (z) lastpos = 64 * tid + 4 * i + ((31 - __clz(z)) >> 3);
         }
         sh.lastpos = lastpos;
@@ -413,6 +340,15 @@ struct alignas(16) ScanShared {
     uint32_t qn;                 // verified-hit queue fill
     alignas(8) uint32_t q[QCAP]; // candidate words (byte kernel) / QCAP/2 {entry, mask} pairs (plane kernel)
 };
+
+// The tile's hit counts for the scan over the tile sums (thread 0, after the
+// tile's last hit record): an overflowed tile's hits all count as cross hits,
+// and a tile that may hold a long cross segment is flagged.
+__device__ __forceinline__ void put_tile_hits(const ScanArgs &a, const ScanShared &sh, uint32_t tile) {
+    a.tsum[tile].nh = sh.nh;
+    a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;   // overflowed: all hits cross
+    if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
+}
 
 // last '\n' (tile-relative) inside 16-byte chunk c at a position < limit, -1 if none
 __device__ __forceinline__ int last_newline_in_chunk(const uint8_t *buf, int c, int limit = 1 << 30) {
@@ -637,39 +573,18 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_pr[2 * KMAX_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint64_t len = a.len;
-    const bool halo = tid < NCH_FRONT + NCH_BACK;
-    const int hc = tid < NCH_FRONT ? tid : NCH_FRONT + NCH_MAIN + (tid - NCH_FRONT);
     const uint32_t tile = blockIdx.x;
     const int64_t g0 = (int64_t)tile * TILE;
     {
-        // every tile but the first / last has its halos inside [0, len): plain
-        // 16-B loads with no per-chunk bounds logic, all issued back to back
-        uint4 v[4];
-        uint4 vh = make_uint4(0, 0, 0, 0);
-        if (g0 - FH >= 0 && (uint64_t)(g0 + TILE + BH) <= len) {
-            const uint8_t *src = a.data + g0 + 16 * tid;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = *(const uint4 *)(src + 16 * TPB * i);
-            // every lane loads (lanes >= 9 repeat chunk 0): no divergent load, so no early wait
-            vh = *(const uint4 *)(a.data + g0 - FH + 16 * (halo ? hc : 0));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = load_chunk(a.data, g0 + (int64_t)(tid + TPB * i) * 16, len);
-            if (halo) vh = load_chunk(a.data, g0 - FH + (int64_t)hc * 16, len);
-        }
+        TileRegs r;
+        load_tile(a.data, len, g0, r);
         if (tid == 0) {
             sh.last_chunk = -1;
             sh.nh = 0;
             sh.nx = 0;
             sh.qn = 0;
         }
-        uint32_t orall = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            orall |= v[i].x | v[i].y | v[i].z | v[i].w;
-            *(uint4 *)(buf + FH + (tid + TPB * i) * 16) = v[i];
-        }
-        if (halo) *(uint4 *)(buf + hc * 16) = vh;
+        const uint32_t orall = store_tile(r, buf);
         if (tid < 2 * KMAX_TILE) s_pr[tid] = a.PR[tid];     // (behind the tile loads)
         if (orall & 0x80808080u) atomicOr(a.err, ERR_NONASCII);
     }
@@ -694,12 +609,7 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
         } else {
             const int64_t gc = g0 + (int64_t)c * 16;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t n = (int64_t)len - (gc + 4 * j);
-                uint32_t z = nl_flags(x[j]);
-                z = n <= 0 ? 0u : n < 4 ? (z & ((1u << (8 * n)) - 1u)) : z;
-                cnt += __popc(z);
-            }
+            for (int j = 0; j < 4; ++j) cnt += __popc(nl_flags_below(x[j], (int64_t)len - (gc + 4 * j)));
         }
         if (do_swar) {
 #pragma unroll
@@ -805,15 +715,9 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
     for (uint32_t h = tid; h < nq; h += TPB) scan_word<WIDE>(a, buf, sh, tile, pw, sh.q[h]);
     if (nq > 64 || sh.qn > QCAP) {
         __syncthreads();         // uniform: every wave may have written records
-        if (tid == 0) {
-            a.tsum[tile].nh = sh.nh;
-            a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;   // overflowed: all hits cross
-            if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
-        }
+        if (tid == 0) put_tile_hits(a, sh, tile);
     } else if (tid == 0) {                       // wave 0 wrote them all (a word can hold 8 hits)
-        a.tsum[tile].nh = sh.nh;
-        a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;
-        if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
+        put_tile_hits(a, sh, tile);
     }
 }
 
@@ -887,36 +791,18 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     __shared__ __attribute__((aligned(16))) uint8_t s_pr[2 * KMAX_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint64_t len = a.len;
-    const bool halo = tid < NCH_FRONT + NCH_BACK;
-    const int hc = tid < NCH_FRONT ? tid : NCH_FRONT + NCH_MAIN + (tid - NCH_FRONT);
     const uint32_t tile = blockIdx.x;
     const int64_t g0 = (int64_t)tile * TILE;
     {
-        uint4 v[4];
-        uint4 vh = make_uint4(0, 0, 0, 0);
-        if (g0 - FH >= 0 && (uint64_t)(g0 + TILE + BH) <= len) {
-            const uint8_t *src = a.data + g0 + 16 * tid;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = *(const uint4 *)(src + 16 * TPB * i);
-            vh = *(const uint4 *)(a.data + g0 - FH + 16 * (halo ? hc : 0));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = load_chunk(a.data, g0 + (int64_t)(tid + TPB * i) * 16, len);
-            if (halo) vh = load_chunk(a.data, g0 - FH + (int64_t)hc * 16, len);
-        }
+        TileRegs r;
+        load_tile(a.data, len, g0, r);
         if (tid == 0) {
             sh.last_chunk = -1;
             sh.nh = 0;
             sh.nx = 0;
             sh.qn = 0;
         }
-        uint32_t orall = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            orall |= v[i].x | v[i].y | v[i].z | v[i].w;
-            *(uint4 *)(buf + FH + (tid + TPB * i) * 16) = v[i];
-        }
-        if (halo) *(uint4 *)(buf + hc * 16) = vh;
+        const uint32_t orall = store_tile(r, buf);
         if (tid < 2 * KMAX_TILE) s_pr[tid] = a.PR[tid];
         if (orall & 0x80808080u) atomicOr(a.err, ERR_NONASCII);
     }
@@ -924,18 +810,7 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
 
     // ---- this thread's 64 bytes (4 chunks) + 4 look-ahead bytes ----
     uint32_t w[17];
-    {
-        const uint4 *src = (const uint4 *)(buf + FH + 64 * tid);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint4 x = src[j];
-            w[4 * j] = x.x;
-            w[4 * j + 1] = x.y;
-            w[4 * j + 2] = x.z;
-            w[4 * j + 3] = x.w;
-        }
-        w[16] = *(const uint32_t *)(buf + FH + 64 * tid + 64);
-    }
+    load_thread_words(buf + FH + 64 * tid, w);
     const bool tail_tile = (uint64_t)(g0 + TILE) > len;
     const uint32_t k0a = 0x0A0A0A0Au, k7f = 0x7F7F7F7Fu;
     uint32_t ccnt[4];
@@ -949,12 +824,7 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
         } else {
             const int64_t gc = g0 + 64 * tid + 16 * j;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int64_t n = (int64_t)len - (gc + 4 * i);
-                uint32_t z = nl_flags(w[4 * j + i]);
-                z = n <= 0 ? 0u : n < 4 ? (z & ((1u << (8 * n)) - 1u)) : z;
-                cnt += __popc(z);
-            }
+            for (int i = 0; i < 4; ++i) cnt += __popc(nl_flags_below(w[4 * j + i], (int64_t)len - (gc + 4 * i)));
         }
         ccnt[j] = cnt;
     }
@@ -1117,15 +987,9 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     }
     if (nq > 64 || sh.qn > QE) {
         __syncthreads();
-        if (tid == 0) {
-            a.tsum[tile].nh = sh.nh;
-            a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;
-            if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
-        }
+        if (tid == 0) put_tile_hits(a, sh, tile);
     } else if (tid == 0) {
-        a.tsum[tile].nh = sh.nh;
-        a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;
-        if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
+        put_tile_hits(a, sh, tile);
     }
 }
 
@@ -1175,17 +1039,8 @@ __device__ __forceinline__ uint64_t resolve_hit(const HitArgs &a, uint64_t pos_l
                 key = (strand ? revcomp_code(r.code, a.k) : r.code) & a.smask;
             }
         } else {
-            const unsigned long long n = atomicAdd(a.rec_count, 1ull);
-            if (n < a.rec_cap) {
-                Record rec;
-                rec.order = order;
-                rec.pos = (uint64_t)t * TILE + (uint64_t)(int64_t)s0;
-                rec.len = a.k;
-                rec.strand = strand;
-                a.recs[n] = rec;
-            } else {
-                atomicOr(a.err, ERR_REC_OVERFLOW);
-            }
+            append_record(a.recs, a.rec_count, a.rec_cap, a.err, order, (uint64_t)t * TILE + (uint64_t)(int64_t)s0, a.k,
+                          strand);
         }
     }
     return key;
@@ -1553,17 +1408,9 @@ __global__ __launch_bounds__(256) void windows_kernel(WindowArgs a) {
                     ok = c == a.P[b];
                 }
                 if (!ok) continue;
-                unsigned long long n = atomicAdd(a.rec_count, 1ull);
-                if (n < a.rec_cap) {
-                    Record r;
-                    r.order = (sl.line_index << (a.pbits + 1)) | ((uint64_t)strand << a.pbits) | j;
-                    r.pos = strand ? sl.start + (L - hi) : sl.start + lo;
-                    r.len = (uint32_t)klen;
-                    r.strand = strand;
-                    a.recs[n] = r;
-                } else {
-                    atomicOr(a.err, ERR_REC_OVERFLOW);
-                }
+                append_record(a.recs, a.rec_count, a.rec_cap, a.err,
+                              (sl.line_index << (a.pbits + 1)) | ((uint64_t)strand << a.pbits) | j,
+                              strand ? sl.start + (L - hi) : sl.start + lo, (uint32_t)klen, strand);
             }
         }
     }
@@ -1836,18 +1683,7 @@ __global__ __launch_bounds__(256) void gen_cand_kernel(GenWinArgs a, PlaneArgs p
         }
         __syncthreads();
         uint32_t w[17];
-        {
-            const uint4 *src = (const uint4 *)(buf + 64 * tid);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint4 x = src[j];
-                w[4 * j] = x.x;
-                w[4 * j + 1] = x.y;
-                w[4 * j + 2] = x.z;
-                w[4 * j + 3] = x.w;
-            }
-            w[16] = *(const uint32_t *)(buf + 64 * tid + 64);
-        }
+        load_thread_words(buf + 64 * tid, w);
         // planes of the 68 bytes (as scan_planes_kernel: one v_dot4 per 8 bases and plane)
         const uint32_t W0 = 0x08040201u;
         uint32_t L[3], H[3];
@@ -1932,9 +1768,7 @@ __global__ __launch_bounds__(256) void gen_cand_kernel(GenWinArgs a, PlaneArgs p
                 if (qi < GC_Q) {
                     q[qi] = r;
                 } else {                                   // (a crowded tile: straight to the list)
-                    const unsigned long long gi = atomicAdd(a.rec_count, 1ull);
-                    if (gi < a.rec_cap) a.recs[gi] = r;
-                    else atomicOr(a.err, ERR_REC_OVERFLOW);
+                    append_record(a.recs, a.rec_count, a.rec_cap, a.err, r.order, r.pos, r.len, r.strand);
                 }
             }
         }
@@ -2177,21 +2011,6 @@ __device__ __forceinline__ uint64_t window_code(const uint8_t *p, uint32_t k, bo
     }
     *exotic = ex;
     return code;
-}
-
-__device__ __forceinline__ void win_record(const WinArgs &a, uint64_t order, uint64_t pos, uint32_t strand,
-                                           uint32_t len) {
-    const unsigned long long n = atomicAdd(a.rec_count, 1ull);
-    if (n < a.rec_cap) {
-        Record rec;
-        rec.order = order;
-        rec.pos = pos;
-        rec.len = len;
-        rec.strand = strand;
-        a.recs[n] = rec;
-    } else {
-        atomicOr(a.err, ERR_REC_OVERFLOW);
-    }
 }
 
 // (an invalid key's order is never read -- compaction, exchange and the heads
@@ -2479,8 +2298,8 @@ __global__ __launch_bounds__(256) void windows_packed_kernel(WinArgs a) {
             if (fw) win_place(a, rf, (mf && !exotic) ? (code & a.smask) : a.invalid_key, of);
             if (rv) win_place(a, rr, (mr && !exotic) ? (rc & a.smask) : a.invalid_key, orr);
             if (exotic) {
-                if (mf && fw) win_record(a, of, pos, 0, k);
-                if (mr && rv) win_record(a, orr, pos, 1, k);
+                if (mf && fw) append_record(a.recs, a.rec_count, a.rec_cap, a.err, of, pos, k, 0);
+                if (mr && rv) append_record(a.recs, a.rec_count, a.rec_cap, a.err, orr, pos, k, 1);
             }
         }
         if (step == 1 || Ws >= W) continue;
@@ -2498,8 +2317,8 @@ __global__ __launch_bounds__(256) void windows_packed_kernel(WinArgs a) {
                 ok = c == a.P[b];
             }
             // the reverse strand's S[p, L) is rc of the line's first L - p bytes
-            if (ok) win_record(a, lo | ((uint64_t)strand << a.pbits) | j, sl.start + (strand ? 0 : p), strand,
-                               (uint32_t)len);
+            if (ok) append_record(a.recs, a.rec_count, a.rec_cap, a.err, lo | ((uint64_t)strand << a.pbits) | j,
+                                  sl.start + (strand ? 0 : p), (uint32_t)len, strand);
         }
         if (plen == 0 && lane == 0) {
             const uint64_t j0 = (L + step - 1) / step;   // first index whose substring is ""
@@ -2683,12 +2502,6 @@ __global__ __launch_bounds__(256) void gather_u64_kernel(const uint64_t *src, co
         dst[i] = src[idx[i]];
 }
 
-__global__ __launch_bounds__(256) void gather_u32_kernel(const uint32_t *src, const uint32_t *idx, uint64_t n,
-                                                         uint32_t *dst) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        dst[i] = src[idx[i]];
-}
-
 // after apply_cross the cross slots hold their entry's index: put the key there
 __global__ __launch_bounds__(256) void cross_wide_fix_kernel(const uint32_t *xslot, uint64_t n, const uint64_t *xkeyl,
                                                              const uint64_t *xkeyh, uint64_t *rkey, uint64_t *rkeyh) {
@@ -2818,19 +2631,6 @@ __global__ __launch_bounds__(256) void bucket_offsets_kernel(const uint32_t *H, 
     if (tid == 0) *ticket = 0;
 }
 
-// (race probes for bucket_scatter_kernel, in experiment builds only: see the
-// Makefile's probes target and tools/bkt_race_probe.py)
-#if defined(KMERHIP_EXPERIMENTS) && defined(KMERHIP_PROBE_BKT_DELAY)
-#define BKT_PROBE_DELAY 1
-#else
-#define BKT_PROBE_DELAY 0
-#endif
-#if defined(KMERHIP_EXPERIMENTS) && defined(KMERHIP_PROBE_BKT_NOFIX)
-#define BKT_PROBE_NOFIX 1
-#else
-#define BKT_PROBE_NOFIX 0
-#endif
-
 // Scatter with the block's elements first grouped by bucket in LDS, so that
 // each bucket's run goes out as one contiguous (coalesced) piece.
 __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
@@ -2884,19 +2684,10 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key
     }
     const uint32_t valid = wtot[0] + wtot[1] + wtot[2] + wtot[3];
     __syncthreads();
-#if BKT_PROBE_DELAY
-    // race probe (experiment build only): waves 1..3 start placing late, so
-    // wave 0 reaches the rewrite of cnt[] below first
-    if (threadIdx.x >= 64)
-        for (int z = 0; z < 64; ++z) __builtin_amdgcn_s_sleep(127);
-#endif
 #pragma unroll
     for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
         if (kk[u] != invalid) {
             const uint32_t p = cnt[kk[u] >> shift] + li[u];
-#if BKT_PROBE_DELAY
-            if (p >= BKT_EPB) continue;             // (the probe keeps a raced store in range)
-#endif
             skey[p] = kk[u];
             srank[p] = (uint32_t)(base + u * 256 + threadIdx.x);
         }
@@ -2905,9 +2696,7 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key
     // this barrier a wave that got here first overwrote a bucket's local start
     // while a slower wave still placed keys by it: keys landed in wrong skey
     // slots, and stale slots went out -- the intermittent lost counts / keys)
-#if !BKT_PROBE_NOFIX
     __syncthreads();
-#endif
     // cnt[b] := global position of local element 0 of bucket b (mod 2^32:
     // element e of bucket b goes to cnt[b] + e)
 #pragma unroll
@@ -2920,10 +2709,6 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key
     for (uint32_t e = threadIdx.x; e < valid; e += 256) {
         const uint32_t k = skey[e], b = k >> shift;
         const uint32_t pos = cnt[b] + e;
-#if BKT_PROBE_DELAY
-        // (the probe keeps a raced store, and the ranks later kernels index by, in range)
-        if (b >= nb || pos >= n || srank[e] >= n) continue;
-#endif
         pkey[pos] = (uint16_t)(k & lo_mask);
         prank[pos] = srank[e];
     }
@@ -3748,10 +3533,6 @@ hipError_t launch_compact_write(const uint32_t *k32, const uint64_t *k64, const 
     return hipGetLastError();
 }
 
-hipError_t launch_gather_u32(const uint32_t *src, const uint32_t *idx, uint64_t n, uint32_t *dst, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_for(n)), dim3(256), 0, s, src, idx, n, dst);
-    return hipGetLastError();
-}
 hipError_t launch_gather_u64(const uint64_t *src, const uint32_t *idx, uint64_t n, uint64_t *dst, hipStream_t s) {
     if (n) hipLaunchKernelGGL(gather_u64_kernel, dim3(grid_for(n)), dim3(256), 0, s, src, idx, n, dst);
     return hipGetLastError();

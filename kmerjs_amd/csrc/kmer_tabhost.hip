@@ -443,7 +443,7 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     f.out = c->t_ent;
     f.nd = c->tnd.p;
     const uint64_t mean = (n - std::min(n, c->t_fill)) / TAB_NQ;   // (keys, not filler slots)
-    uint64_t range_keys = 3000;               // mean keys per LDS range (load ~0.37: short probes; measured best at C3)
+    uint64_t range_keys = 3000;               // mean keys per LDS range (load ~0.37: short probing; measured best at C3)
     if (const char *rk = exp_env("KMERHIP_TAB_RANGE")) range_keys = std::max<uint64_t>(64, strtoull(rk, nullptr, 10));
     while (f.sub_bits < 16 && (mean >> f.sub_bits) > range_keys) ++f.sub_bits;
     f.range_keys = (uint32_t)std::min<uint64_t>(range_keys, TAB_CAP);

@@ -35,7 +35,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "kmer_internal.hpp"
+#include "kmer_device.hpp"
 
 namespace kmerhip {
 
@@ -47,21 +47,11 @@ constexpr int TAB_ROUND = TAB_RPL * TAB_WG1; // keys sorted in LDS per round
 constexpr uint64_t TAB_EMPTY = 1ull << 63;   // empty slot (remainders are < 2^44)
 constexpr uint64_t TAB_RMASK = (1ull << TAB_RBITS) - 1;
 
-__device__ __forceinline__ uint32_t tab_incl_sum(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return x;
-}
-
 // Exclusive scan of one value per thread over a 1024-thread workgroup;
 // `ws` = 16 words of LDS scratch.  Returns the exclusive prefix, *total the sum.
 __device__ __forceinline__ uint32_t block_excl_1024(uint32_t v, uint32_t *ws, uint32_t *total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t inc = tab_incl_sum(v);
+    const uint32_t inc = wave_incl_sum(v);
     if (lane == 63) ws[wid] = inc;
     __syncthreads();
     uint32_t before = 0, all = 0;
@@ -78,7 +68,7 @@ __device__ __forceinline__ uint32_t block_excl_1024(uint32_t v, uint32_t *ws, ui
 // exclusive scan of one value per thread over a 512-thread workgroup (ws: 8 words)
 __device__ __forceinline__ uint32_t block_excl_512(uint32_t v, uint32_t *ws, uint32_t *total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t inc = tab_incl_sum(v);
+    const uint32_t inc = wave_incl_sum(v);
     if (lane == 63) ws[wid] = inc;
     __syncthreads();
     uint32_t before = 0, all = 0;
@@ -91,11 +81,6 @@ __device__ __forceinline__ uint32_t block_excl_512(uint32_t v, uint32_t *ws, uin
     *total = all;
     return before + inc - v;
 }
-__device__ __forceinline__ uint32_t readlane32(uint32_t v, uint32_t i) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
-}
-
-
 
 // A wave's position in its workgroup's share of sequence lines.
 struct TabCur {
@@ -114,20 +99,6 @@ __device__ __forceinline__ void tab_fetch(const TabArgs &a, TabCur &c) {
     if (lane < 16 && mi < c.end) {
         c.dstart = a.lines[mi].start;
         c.dlen = a.lines[mi].len;
-    }
-}
-
-__device__ __forceinline__ void tab_record(const TabArgs &a, uint64_t pos, uint32_t strand) {
-    const unsigned long long i = atomicAdd(a.rec_count, 1ull);
-    if (i < a.rec_cap) {
-        Record r;
-        r.order = 0;
-        r.pos = pos;
-        r.len = a.k;
-        r.strand = strand;
-        a.recs[i] = r;
-    } else {
-        atomicOr(a.err, ERR_REC_OVERFLOW);
     }
 }
 
@@ -172,7 +143,7 @@ __device__ __forceinline__ uint32_t tab_round(const TabArgs &a, TabCur &c, bool 
     const uint64_t W = c.dlen >= k ? c.dlen - k + 1 : 0;          // windows of the line
     const uint64_t rem = lane == 0 ? (W > c.seg ? W - c.seg : 0) : W;
     const uint32_t need = lane < 16 ? (uint32_t)((rem + NS - 1) / NS) : 0u;   // (<= 2^32 lanes: pieces are short)
-    const uint32_t cum = tab_incl_sum(need);                      // inclusive over lanes 0..15
+    const uint32_t cum = wave_incl_sum(need);                      // inclusive over lanes 0..15
     const uint32_t tot = readlane32(cum, 15);
     // this lane's line: the first i with cum_i > lane
     uint32_t li = 0;
@@ -275,10 +246,10 @@ __device__ __forceinline__ uint32_t tab_round(const TabArgs &a, TabCur &c, bool 
         } else if (rec) {
             const uint64_t pos = st + w0 + m;
             if (a.canonical) {
-                tab_record(a, pos, 0);
+                append_record(a.recs, a.rec_count, a.rec_cap, a.err, 0, pos, a.k, 0);
             } else {
-                if (fm) tab_record(a, pos, 0);
-                if (rm) tab_record(a, pos, 1);
+                if (fm) append_record(a.recs, a.rec_count, a.rec_cap, a.err, 0, pos, a.k, 0);
+                if (rm) append_record(a.recs, a.rec_count, a.rec_cap, a.err, 0, pos, a.k, 1);
             }
         }
     }
@@ -768,8 +739,8 @@ __global__ __launch_bounds__(TAB_WG1) void tab_scatter2c_kernel(const uint64_t *
 // offset b = b gmag >> 20), whose summed count is again near its mean (C5: 11
 // buckets, ~5.3 K keys, 8 % slack); the final sorts a region's keys by bucket
 // anyway.  Fewer, larger regions also give longer write-out runs.
-// NAR (narrow keys, k <= 21: h's low 22 bits are 0): B2 holds the 32-bit key
-// (uint32_t)(h >> 22) = bucket offset << 22 | the remainder's top 22 bits (the
+// NAR (narrow keys, k <= 21: h's low 23 bits are 0): B2 holds the 32-bit key
+// (uint32_t)(h >> 23) = bucket offset << 21 | the remainder's top 21 bits (the
 // partition is the region's), half the bytes; the LDS sort runs on those
 // 32-bit keys and the write-out aligns to 16 keys (64 B).
 // B1N: pass-1 keys of 32 bits (narrow, from this session's pass 1)
@@ -1078,7 +1049,7 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
     };
     // a unit's keys (lanes past its end re-read its first key and are masked
     // at use): unconditional loads, all in flight together
-    // (narrow B2, b2n: 32-bit keys h >> 22 without the partition bits, which
+    // (narrow B2, b2n: 32-bit keys h >> 23 without the partition bits, which
     // come from the unit's bucket ux)
     auto load_keys = [&](uint32_t ux, uint64_t s0x, uint64_t nx) {
         if (nx - 1 < (uint64_t)TAB_REG_MAX) {
@@ -1224,7 +1195,7 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
         // into 4,096 LDS bins by their top 12 bits, then every thread dedupes
         // its 4 adjacent bins (~11 keys at C3) by comparison: one returning
         // LDS atomic per key and plain LDS stores, instead of a CAS + a count
-        // add per key (plus probes) and a slot scan per range.  A unit with a
+        // add per key (plus probing) and a slot scan per range.  A unit with a
         // crowded run of bins (many copies of one key) takes the hash path below.
         if (inreg && !(KH_ABLATE(a) & 4)) {
             // bins: the top 12 bits of (bucket offset << 44 | remainder), so a
@@ -1630,7 +1601,7 @@ __global__ __launch_bounds__(TAB_SWG, 4) void tab_sort_final_kernel(TabFinal a) 
         // live: ONE bucket of 64-bit keys (its bin fixes the remainder's top
         // bits: 32-bit LDS entries), a GRoup of buckets of 64-bit keys (64-bit
         // entries, half the keys), and NARrow keys (a fixed region of 32-bit
-        // keys, bucket offset << 22 | the remainder's top 22 bits: one bucket
+        // keys, bucket offset << 21 | the remainder's top 21 bits: one bucket
         // or a group, 32-bit entries, all the keys).  Held keys: lo = low 32
         // bits (narrow: the key), hi = the rest (a group's), pk = bin, later
         // bin << 14 | sorted position.  Returns false when a bin is crowded.
