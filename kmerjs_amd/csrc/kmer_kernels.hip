@@ -366,32 +366,141 @@ __device__ __forceinline__ int last_newline_in_chunk(const uint8_t *buf, int c, 
     return last;
 }
 
-// One verified prefix hit (queue entry (q << 1) | strand): window analysis,
-// tile-local line context, hit record.
-// THREAD_MAP: sh.nlmap holds one bit per 64-byte thread region (plane
-// kernel; chunks inside a region are resolved through cpre), else one bit per
-// 16-byte chunk (byte kernel).
 // bytes [from, to) of a 32-bit word (clamped to 0..4)
-__device__ __forceinline__ uint32_t byte_range_mask(int from, int to) {
+__host__ __device__ constexpr uint32_t byte_range_mask(int from, int to) {
     from = from < 0 ? 0 : from > 4 ? 4 : from;
     to = to < 0 ? 0 : to > 4 ? 4 : to;
     const uint32_t a = to >= 4 ? ~0u : (1u << (8 * to)) - 1u, b = from >= 4 ? ~0u : (1u << (8 * from)) - 1u;
     return a & ~b;
 }
 
+// x ^ "ACGT"[code of each byte]: zero exactly at the bytes that are A, C, G or T
+__device__ __forceinline__ uint32_t acgt_diff(uint32_t x) {
+    const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
+    return __builtin_amdgcn_perm(0u, 0x54474341u, c) ^ x;
+}
+
+// Tile-local line context of a window start s0 > 0, byte kernel (sh.nlmap
+// holds one bit per 16-byte chunk): c_local = '\n' count of the tile before
+// s0, lstart = one past the last '\n' before s0 (-1: none in this tile).
+__device__ __forceinline__ void line_context_chunks(const uint8_t *buf, const ScanShared &sh, int s0,
+                                                    uint32_t &c_local, int &lstart) {
+    const int cs = (s0 - 1) >> 4;               // chunk holding byte s0-1
+    const uint4 x4 = *(const uint4 *)(buf + FH + 16 * cs);
+    const uint32_t xs[4] = {x4.x, x4.y, x4.z, x4.w};
+    uint32_t cnt = 0;
+    int last = -1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int pos = 16 * cs + 4 * j;
+        const int rem = s0 - pos;
+        uint32_t z = nl_flags(xs[j]);
+        z = rem <= 0 ? 0u : rem < 4 ? (z & ((1u << (8 * rem)) - 1u)) : z;
+        cnt += __popc(z);
+        last = z ? pos + ((31 - __clz(z)) >> 3) : last;
+    }
+    c_local = (uint32_t)sh.cpre[cs] + cnt;
+    if (last >= 0) {
+        lstart = last + 1;
+    } else if (c_local > 0) {
+        // the line started in the last earlier chunk that holds a '\n'
+        const int cc = cs - 1;
+        int wi = cc >> 5;
+        uint32_t m = sh.nlmap[wi] & (0xFFFFFFFFu >> (31 - (cc & 31)));
+        while (m == 0) m = sh.nlmap[--wi];
+        lstart = last_newline_in_chunk(buf, 32 * wi + 31 - __clz(m)) + 1;
+    }
+}
+
+// bit i: byte i of a 16-byte chunk is '\n' (ASCII bytes).  Per word one
+// v_xad (bit 7 of a byte set: not '\n'), an and, and a v_dot4 whose weights
+// put the word's four flags side by side (times 128).
+__device__ __forceinline__ uint32_t chunk_nl_mask(uint4 x) {
+    const uint32_t k0a = 0x0A0A0A0Au, k7f = 0x7F7F7F7Fu;
+    const uint32_t lo = __builtin_amdgcn_udot4(not_nl_bits_xad(x.y, k0a, k7f), 0x80402010u,
+                            __builtin_amdgcn_udot4(not_nl_bits_xad(x.x, k0a, k7f), 0x08040201u, 0u, false), false);
+    const uint32_t hi = __builtin_amdgcn_udot4(not_nl_bits_xad(x.w, k0a, k7f), 0x80402010u,
+                            __builtin_amdgcn_udot4(not_nl_bits_xad(x.z, k0a, k7f), 0x08040201u, 0u, false), false);
+    return ~((lo >> 7) | (hi << 1)) & 0xFFFFu;
+}
+
+// The same for the plane kernel (sh.nlmap holds one bit per 64-byte thread
+// region; the chunks of a region are told apart by cpre), as ONE route for
+// every lane: the pass runs with a dozen lanes whose lines start at any
+// distance, so every branch of a case split would be executed anyway.
+//   round 1 (addresses depend on s0 only, issued with the window's reads):
+//            the chunk of s0-1, the cpre quad of its region, two bitmap words;
+//   round 2: the cpre quad (+ the next cpre) of the region R that holds the
+//            last '\n' before s0 -- s0's own region, or the highest bitmap
+//            bit below it;
+//   round 3: the chunk of R where cpre rises last, and its last '\n' before s0.
+// The two bitmap words reach 32..63 regions (2..4 KiB) back; a line that
+// starts further back walks the bitmap (a loop no FASTQ read enters).
+// want = false (window rejected, or s0 <= 0): c_local = 0, lstart = -1; the
+// reads are clamped into the tile, so such a lane is harmless.
+__device__ __forceinline__ void line_context_regions(const uint8_t *buf, const ScanShared &sh, int s0, bool want,
+                                                     uint32_t &c_local, int &lstart) {
+    const int cs = (s0 > 0 ? s0 - 1 : 0) >> 4;  // chunk holding byte s0-1
+    const int rg = cs >> 2, wi = rg >> 5;       // its region, the region's bitmap word
+    const uint4 x4 = *(const uint4 *)(buf + FH + 16 * cs);
+    const uint2 c2 = *(const uint2 *)(sh.cpre + 4 * rg);
+    const uint32_t mhi = sh.nlmap[wi], mlo = sh.nlmap[wi > 0 ? wi - 1 : 0];
+    // '\n' of chunk cs before s0 (a lane with s0 <= 0 counts garbage: not wanted)
+    const uint32_t cnt = __popc(__builtin_amdgcn_ubfe(chunk_nl_mask(x4), 0u, (uint32_t)(s0 - 16 * cs)));
+    const uint32_t ccs = (uint32_t)((((uint64_t)c2.y << 32) | c2.x) >> (16 * (cs & 3))) & 0xFFFFu;
+    const uint32_t cl = ccs + cnt;
+    const bool has = want && cl > 0;             // a '\n' before s0 in this tile
+    // R: s0's region if the '\n' is in chunk cs or in an earlier chunk of the
+    // region (cpre rose inside it), else the highest bitmap bit below rg
+    int R = rg;
+    if (has && cnt == 0 && ccs == (c2.x & 0xFFFFu)) {
+        const uint64_t m = (((uint64_t)mhi << 32) | (wi > 0 ? mlo : 0u)) & ((1ull << (32 + (rg & 31))) - 1ull);
+        R = 32 * (wi - 1) + 63 - (int)__clzll((long long)m);
+        if (m == 0) {                            // (cpre[4 * rg] > 0: an earlier word has a bit)
+            int w = wi - 1;
+            uint32_t mm;
+            do mm = sh.nlmap[--w]; while (mm == 0);
+            R = 32 * w + 31 - __clz(mm);
+        }
+    }
+    const uint2 d2 = *(const uint2 *)(sh.cpre + 4 * R);
+    const uint32_t nxt = sh.cpre[min(4 * R + 4, NCH_MAIN - 1)];   // (used for R < rg only: 4R + 4 <= 4rg)
+    const uint32_t d[4] = {d2.x & 0xFFFFu, d2.x >> 16, d2.y & 0xFFFFu, d2.y >> 16};
+    const int jl = R == rg ? cs - 4 * rg : 4;    // chunks [0, jl) of R lie before chunk cs
+    const int jc = (jl > 3 && d[3] < nxt) ? 3 : (jl > 2 && d[2] < d[3]) ? 2 : (jl > 1 && d[1] < d[2]) ? 1 : 0;
+    const int c = cnt ? cs : 4 * R + jc;
+    const uint4 y4 = *(const uint4 *)(buf + FH + 16 * c);
+    const uint32_t ym = __builtin_amdgcn_ubfe(chunk_nl_mask(y4), 0u, (uint32_t)min(s0 - 16 * c, 16));
+    const int last = 16 * c + 31 - __clz(ym);    // (has: ym != 0)
+    c_local = want ? cl : 0u;
+    lstart = has ? last + 1 : -1;
+}
+
+// One prefix hit (queue entry (q << 1) | strand): window analysis, tile-local
+// line context, hit record.
 // WIDE: k > 32 (the window's first k - 32 bases go to hits_hi / ovf_hi).
-// !THREAD_MAP (the byte kernel, which also serves non-ACGT prefixes): only the
-// suffix bytes decide `exotic` -- the key is P + the suffix's 2-bit code, so a
-// prefix may hold any bytes
-template <bool THREAD_MAP, bool WIDE>
+// K, PLEN: window and prefix length at compile time (0: a.k / a.plen).
+// !THREAD_MAP (the byte kernel, which also serves non-ACGT prefixes): e is a
+// byte-exact prefix match, and only the suffix bytes decide `exotic` -- the
+// key is P + the suffix's 2-bit code, so a prefix may hold any bytes.
+// THREAD_MAP (the plane kernel): e is a plane candidate -- its first pb <= 5
+// prefix bytes agree with P (rc(P) on the reverse strand) on bits 1 and 2, and
+// non-ACGT bytes alias.  The window's ACGT check settles it: if those pb
+// bytes (tile bytes [q, q + pb) on either strand) are all exactly A/C/G/T the
+// plane match is an exact match, else the candidate is dropped; prefix bytes
+// past the fifth are compared with pw (P words, then rc(P) words).
+template <bool THREAD_MAP, bool WIDE, uint32_t K = 0, uint32_t PLEN = 0>
 __device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, ScanShared &sh, uint32_t tile,
-                                      uint32_t e) {
-    const uint32_t k = a.k, plen = a.plen;
+                                         uint32_t e, uint32_t pb = 0, const uint32_t *pw = nullptr) {
+    static_assert((K == 0) == (PLEN == 0) && PLEN <= 5 && PLEN <= K && K <= (WIDE ? KMAX_TILE : KMAX_PACKED),
+                  "fixed k / prefix length: both or neither, prefix fully plane-tested");
+    const uint32_t k = K ? K : a.k, plen = K ? PLEN : a.plen;
     const uint32_t strand = e & 1u;
     const int q = (int)(e >> 1);
     const int s0 = strand ? q + (int)plen - (int)k : q;   // window start, tile-relative
     // window bytes: ACGT check (v_perm against "ACGT"), '\n' check, 2-bit codes
     uint32_t exo_bits = 0, nl_bits = 0;          // (OR-accumulated; tested once)
+    uint32_t pfx_bits = 0;                       // THREAD_MAP: mismatch bits of the prefix bytes
     uint64_t code = 0;
     const int sfx0 = strand ? 0 : (int)plen, sfx1 = strand ? (int)(k - plen) : (int)k;   // suffix bytes
 #pragma unroll 4
@@ -401,12 +510,33 @@ __device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, 
         const uint32_t mk = nb == 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1u);
         const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
         const uint32_t expect = __builtin_amdgcn_perm(0u, 0x54474341u, c);   // "ACGT"[c] per byte
-        const uint32_t mx = THREAD_MAP ? mk : mk & byte_range_mask(sfx0 - (int)b, sfx1 - (int)b);
-        exo_bits |= (expect ^ x) & mx;
+        if (THREAD_MAP && K) {
+            // fixed lengths: the plane-tested bytes [q - s0, q - s0 + PLEN) of the window are constants per strand
+            const uint32_t pf = byte_range_mask(0 - (int)b, (int)PLEN - (int)b),
+                           pr = byte_range_mask((int)K - (int)PLEN - (int)b, (int)K - (int)b);
+            const uint32_t pm = strand ? pr : pf;
+            pfx_bits |= (expect ^ x) & mk & pm;
+            exo_bits |= (expect ^ x) & mk & ~pm;
+        } else {
+            const uint32_t mx = THREAD_MAP ? mk : mk & byte_range_mask(sfx0 - (int)b, sfx1 - (int)b);
+            exo_bits |= (expect ^ x) & mx;
+        }
         nl_bits |= nl_flags(x) & mk;
         // the four 2-bit codes, first byte most significant: c0 * 64 + c1 * 16 + c2 * 4 + c3
         const uint32_t pk = __builtin_amdgcn_udot4(c, 0x01041040u, 0u, false);
         code = (code << (2 * nb)) | (pk >> (2 * (4 - nb)));
+    }
+    if (THREAD_MAP && !K) {
+        // run-time lengths: the pb plane-tested bytes once more from q (exo_bits
+        // covers the whole window; where these are exact it is the rest's), and
+        // the prefix bytes past them against P / rc(P)
+        pfx_bits = (acgt_diff(lds_word(buf, q)) & (pb >= 4 ? 0xFFFFFFFFu : ((1u << (8 * pb)) - 1u))) |
+                   (acgt_diff(lds_word(buf, q + 4)) & (pb > 4 ? 0xFFu : 0u));
+        for (uint32_t b = 4; b < plen && plen > 5; b += 4) {
+            const uint32_t n = plen - b;
+            const uint32_t mk = (n >= 4 ? 0xFFFFFFFFu : ((1u << (8 * n)) - 1u)) & (b == 4 ? 0xFFFFFF00u : 0xFFFFFFFFu);
+            pfx_bits |= (lds_word(buf, q + (int)b) ^ pw[(strand ? KMAX_TILE / 4 : 0) + b / 4]) & mk;
+        }
     }
     const bool exotic = exo_bits != 0, hasnl = nl_bits != 0;
     // k > 32: code keeps the last 32 bases; the first k - 32 (the window's
@@ -421,74 +551,19 @@ __device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, 
             chi = (chi << (2 * nb)) | (pk >> (2 * (4 - nb)));
         }
     }
-    // crosses a line end (or the end of input); k == 1: line.length > 1
-    const bool valid = !hasnl && !(k == 1 && buf[FH + s0 - 1] == '\n' && buf[FH + s0 + 1] == '\n');
+    // not a prefix hit after all; crosses a line end (or the end of input); k == 1: line.length > 1
+    const bool valid = pfx_bits == 0 && !hasnl &&
+                       !(k == 1 && buf[FH + s0 - 1] == '\n' && buf[FH + s0 + 1] == '\n');
+    if (THREAD_MAP && (KH_ABLATE(a) & 4u)) {     // experiments: verified, no record
+        if (valid) atomicAdd(&sh.nx, 0u);
+        return;
+    }
     // tile-local line context of the window start: '\n' count before s0 and
-    // the start of its line if that lies inside this tile.  The reads that
-    // only depend on s0 (chunk, cpre of its region, region bitmap word) go
-    // out together; at most two more dependent rounds follow.
+    // the start of its line if that lies inside this tile
     uint32_t c_local = 0;
     int lstart = -1;
-    if (valid && s0 > 0) {
-        const int cs = (s0 - 1) >> 4;               // chunk holding byte s0-1
-        const uint4 x4 = *(const uint4 *)(buf + FH + 16 * cs);
-        uint32_t cp[4] = {0, 0, 0, 0};              // THREAD_MAP: cpre of cs's 64-byte region
-        uint32_t mw = 0;
-        const int rb = cs & ~3;
-        if (THREAD_MAP) {
-            const uint2 c2 = *(const uint2 *)(sh.cpre + rb);
-            cp[0] = c2.x & 0xFFFFu;
-            cp[1] = c2.x >> 16;
-            cp[2] = c2.y & 0xFFFFu;
-            cp[3] = c2.y >> 16;
-            if (rb > 0) mw = sh.nlmap[((rb >> 2) - 1) >> 5];
-        }
-        const uint32_t xs[4] = {x4.x, x4.y, x4.z, x4.w};
-        uint32_t cnt = 0;
-        int last = -1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int pos = 16 * cs + 4 * j;
-            const int rem = s0 - pos;
-            uint32_t z = nl_flags(xs[j]);
-            z = rem <= 0 ? 0u : rem < 4 ? (z & ((1u << (8 * rem)) - 1u)) : z;
-            cnt += __popc(z);
-            last = z ? pos + ((31 - __clz(z)) >> 3) : last;
-        }
-        const uint32_t ccs = THREAD_MAP ? cp[cs - rb] : (uint32_t)sh.cpre[cs];
-        c_local = ccs + cnt;
-        if (last >= 0) {
-            lstart = last + 1;
-        } else if (c_local > 0) {
-            // the line started in the last earlier chunk that holds a '\n'
-            int c = -1;
-            if (THREAD_MAP) {
-                // inside cs's region first: chunk rb + j holds a '\n' iff cpre rises after it
-                if (ccs > cp[0]) {
-#pragma unroll
-                    for (int j = 2; j >= 0; --j)
-                        if (c < 0 && rb + j < cs && cp[j] < ccs) c = rb + j;
-                } else {
-                    const int rr = (rb >> 2) - 1;        // earlier regions: region bitmap
-                    int wi = rr >> 5;
-                    uint32_t m = mw & (0xFFFFFFFFu >> (31 - (rr & 31)));
-                    while (m == 0) m = sh.nlmap[--wi];
-                    const int rg = 4 * (32 * wi + 31 - __clz(m));
-                    const uint2 d2 = *(const uint2 *)(sh.cpre + rg);
-                    const uint32_t nxt = sh.cpre[rg + 4];      // (rg + 4 <= rb <= cs)
-                    const uint32_t d[4] = {d2.x & 0xFFFFu, d2.x >> 16, d2.y & 0xFFFFu, d2.y >> 16};
-                    c = d[3] < nxt ? rg + 3 : d[2] < d[3] ? rg + 2 : d[1] < d[2] ? rg + 1 : rg;
-                }
-            } else {
-                const int cc = cs - 1;               // chunk bitmap
-                int wi = cc >> 5;
-                uint32_t m = sh.nlmap[wi] & (0xFFFFFFFFu >> (31 - (cc & 31)));
-                while (m == 0) m = sh.nlmap[--wi];
-                c = 32 * wi + 31 - __clz(m);
-            }
-            lstart = last_newline_in_chunk(buf, c) + 1;
-        }
-    }
+    if (THREAD_MAP) line_context_regions(buf, sh, s0, valid && s0 > 0, c_local, lstart);
+    else if (valid && s0 > 0) line_context_chunks(buf, sh, s0, c_local, lstart);
     // slots and the cross count: one LDS atomic per wave, not per hit.  The
     // hit kernel ranks hits of lines inside the tile; lines that cross a tile
     // edge are placed at finish (same predicate there).
@@ -722,27 +797,6 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
 }
 
 
-// Plane-kernel candidate (q << 1) | strand: byte-exact prefix check (the
-// planes alias non-ACGT bytes), then the hit record.
-template <bool WIDE>
-__device__ __forceinline__ void verify_emit(const ScanArgs &a, const uint8_t *buf, ScanShared &sh, uint32_t tile,
-                                            const uint32_t *pw, uint32_t e) {
-    const uint32_t strand = e & 1u, plen = a.plen;
-    const int q = (int)(e >> 1);
-    bool ok = true;
-#pragma unroll 1
-    for (uint32_t b = 0; b < plen && ok; b += 4) {
-        const uint32_t n = plen - b;
-        const uint32_t mk = n >= 4 ? 0xFFFFFFFFu : ((1u << (8 * n)) - 1u);
-        ok = ((lds_word(buf, q + (int)b) ^ pw[(strand ? KMAX_TILE / 4 : 0) + b / 4]) & mk) == 0;
-    }
-    if (KH_ABLATE(a) & 4u) {                         // experiments: verified, no record
-        if (ok) atomicAdd(&sh.nx, 0u);
-        return;
-    }
-    if (ok) emit_hit<true, WIDE>(a, buf, sh, tile, e);
-}
-
 // ---------------------------------------------------------------------------
 // Plane kernel (ACGT prefixes).  Same tile staging as scan_tile_kernel, but
 // after the coalesced load each thread works on its own 64 contiguous bytes
@@ -784,7 +838,10 @@ __host__ __device__ constexpr uint32_t plane_masks_const(const char *p, const ch
 }
 constexpr uint32_t PM_ATGAC = plane_masks_const("ATGAC", "GTCAT");
 
-template <bool FULL5, bool WIDE, uint32_t PM = 0>
+// K, PLEN != 0: the reference's default k = 16 with that prefix compiled in as
+// well (launch_scan_planes); the candidate -> hit-record pass is then
+// straight-line code.  0: a.k / a.plen at run time.
+template <bool FULL5, bool WIDE, uint32_t PM = 0, uint32_t K = 0, uint32_t PLEN = 0>
 __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs pa) {
     __shared__ __attribute__((aligned(16))) uint8_t buf[BUFSZ];
     __shared__ ScanShared sh;
@@ -896,7 +953,7 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
         mf[h] = plane_match(L[h], H[h], L[h + 1], H[h + 1], kl, kh, pb, SL, SH);
         mr[h] = plane_match(L[h], H[h], L[h + 1], H[h + 1], rl, rh, pb, SL, SH);
     }
-    if (a.k < a.plen || (KH_ABLATE(a) & 1u)) mf[0] = mf[1] = mr[0] = mr[1] = 0;
+    if ((!K && a.k < a.plen) || (KH_ABLATE(a) & 1u)) mf[0] = mf[1] = mr[0] = mr[1] = 0;
 
     // ---- block scan of the per-thread '\\n' counts -> cpre per chunk ----
     __syncthreads();
@@ -933,13 +990,17 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
 
     // ---- candidates -> LDS queue: one {first window, mask} entry per nonzero
     //      32-position mask (ballot + mbcnt, one LDS atomic per wave); the
-    //      rare, branchy verification runs once per tile in as few waves as
-    //      possible ----
+    //      rare, branchy candidate -> hit-record pass runs once per tile in as
+    //      few waves as possible.  The queue holds QE entries; a tile with
+    //      more (short prefixes, repeats) is drained in rounds of QE (barrier,
+    //      drain, next QE entries), so the kernel holds the pass once ----
     const uint32_t *pw = (const uint32_t *)s_pr;
     uint2 *qe = (uint2 *)sh.q;
     constexpr uint32_t QE = QCAP / 2;
+    static_assert(QE == 128 && QCAP == 256, "a round: one entry per thread of waves 0 and 1, 128 queue words each");
+    const uint32_t mm[4] = {mf[0], mf[1], mr[0], mr[1]};
+    uint32_t qpos[4] = {0, 0, 0, 0};             // queue position of entry hs (where mm[hs] != 0)
     {
-        const uint32_t mm[4] = {mf[0], mf[1], mr[0], mr[1]};
         unsigned long long bl[4];
         uint32_t tot = 0;
 #pragma unroll
@@ -953,44 +1014,58 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
 #pragma unroll
             for (int hs = 0; hs < 4; ++hs) {
-                if (bl[hs]) {
-                    if (mm[hs]) {
-                        const uint32_t pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bl[hs] >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)bl[hs], 0u));
-                        const uint32_t e0 = ((64u * (uint32_t)tid + 32u * (uint32_t)(hs & 1)) << 1) | (uint32_t)(hs >> 1);
-                        if (pos < QE) {
-                            qe[pos] = make_uint2(e0, mm[hs]);
-                        } else {                 // queue full: process in place
-                            uint32_t m = mm[hs];
-                            while (m) {
-                                const uint32_t bit = __ffs(m) - 1;
-                                m &= m - 1;
-                                verify_emit<WIDE>(a, buf, sh, tile, pw, e0 + (bit << 1));
-                            }
-                        }
-                    }
-                    base += (uint32_t)__popcll(bl[hs]);
-                }
+                qpos[hs] = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bl[hs] >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)bl[hs], 0u));
+                base += (uint32_t)__popcll(bl[hs]);
             }
         }
     }
-    __syncthreads();
-    const uint32_t nq = min(sh.qn, QE);
-    for (uint32_t h = tid; h < nq; h += TPB) {
-        const uint2 en = qe[h];
-        uint32_t m = en.y;
-        while (m) {
-            const uint32_t bit = __ffs(m) - 1;
-            m &= m - 1;
-            verify_emit<WIDE>(a, buf, sh, tile, pw, en.x + (bit << 1));
+    // entries [done, done + QE) of the tile into the queue
+    auto enqueue = [&](uint32_t done) {
+#pragma unroll
+        for (int hs = 0; hs < 4; ++hs) {
+            const uint32_t e0 = ((64u * (uint32_t)tid + 32u * (uint32_t)(hs & 1)) << 1) | (uint32_t)(hs >> 1);
+            if (mm[hs] && qpos[hs] - done < QE) qe[qpos[hs] - done] = make_uint2(e0, mm[hs]);
         }
-    }
-    if (nq > 64 || sh.qn > QE) {
+    };
+    enqueue(0);
+    __syncthreads();
+    const uint32_t total = sh.qn;                // (final: every wave's atomic is behind the barrier)
+    // the usual tile: wave 0 drains alone and no barrier follows, so the other
+    // waves leave here -- before the loop, whose hoisted set-up they would
+    // otherwise execute for nothing
+    if (total <= 64 && wid != 0) return;
+    for (uint32_t done = 0;;) {                  // (uniform)
+        // Entry tid of the round -> its candidates, one per lane: each wave
+        // spreads the set bits of its 64 entries over its own half of the
+        // queue (the entries are in registers by then), 64 candidates at a
+        // time, so a lane with two candidates does not make the wave run the
+        // pass twice.
+        const uint32_t left = total - done;
+        uint2 en = make_uint2(0u, 0u);
+        if ((uint32_t)tid < min(left, QE)) en = qe[tid];
+        const uint32_t nc = __popc(en.y), incl = wave_incl_sum(nc);
+        const uint32_t wtot = readlane32(incl, 63);
+        uint32_t *flat = sh.q + 128 * (wid & 1);
+        for (uint32_t cb = 0; cb < wtot; cb += 64) {
+            uint32_t m = en.y, p = incl - nc - cb;       // (wraps below cb: not in this batch)
+            while (m) {
+                const uint32_t bit = __ffs(m) - 1;
+                m &= m - 1;
+                if (p < 64) flat[p] = en.x + (bit << 1);
+                ++p;
+            }
+            if ((uint32_t)lane < min(wtot - cb, 64u))
+                emit_hit<true, WIDE, K, PLEN>(a, buf, sh, tile, flat[lane], pb, pw);
+        }
+        if (left <= QE) break;
+        __syncthreads();         // the round's entries are read before the next round's are written
+        done += QE;
+        enqueue(done);
         __syncthreads();
-        if (tid == 0) put_tile_hits(a, sh, tile);
-    } else if (tid == 0) {
-        put_tile_hits(a, sh, tile);
     }
+    if (total > 64) __syncthreads();             // more than wave 0 wrote records
+    if (tid == 0) put_tile_hits(a, sh, tile);
 }
 
 // Resolve one hit: global line index / line start from the tile scans, the
@@ -3305,7 +3380,9 @@ hipError_t launch_scan_planes(const ScanArgs &a, const PlaneArgs &pa, hipStream_
         pm |= (pa.kl[i] ? 1u : 0u) << (4 * i) | (pa.kh[i] ? 1u : 0u) << (4 * i + 1) |
               (pa.rl[i] ? 1u : 0u) << (4 * i + 2) | (pa.rh[i] ? 1u : 0u) << (4 * i + 3);
     if (pa.pb >= 5 && pm == PM_ATGAC) {     // the default prefix, compiled in
-        if (a.k > 32) hipLaunchKernelGGL((scan_planes_kernel<true, true, PM_ATGAC>), g, dim3(TPB), 0, s, a, pa);
+        if (a.k == 16 && a.plen == 5)        // ... and the default k with it (a longer prefix may begin with ATGAC)
+            hipLaunchKernelGGL((scan_planes_kernel<true, false, PM_ATGAC, 16, 5>), g, dim3(TPB), 0, s, a, pa);
+        else if (a.k > 32) hipLaunchKernelGGL((scan_planes_kernel<true, true, PM_ATGAC>), g, dim3(TPB), 0, s, a, pa);
         else hipLaunchKernelGGL((scan_planes_kernel<true, false, PM_ATGAC>), g, dim3(TPB), 0, s, a, pa);
         return hipGetLastError();
     }
