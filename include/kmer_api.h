@@ -258,7 +258,36 @@ kmer_status kmer_synth_fastq_device(void *d_out, uint64_t seed, uint64_t first_r
  *   keys      = distinct Map keys (both orientations, prefix-filtered, + records),
  *   total     = sum of the Map's counts (= counted windows on both strands). */
 kmer_status kmer_table_stats(kmer_ctx *ctx, uint64_t *canonical, uint64_t *keys, uint64_t *total);
-/* The table itself, in device memory.  2^20 buckets; bucket q holds
+/* Batched lookup against the table (after a finish): the Map's `get` for n
+ * query keys of exactly k bytes each, back to back; counts[i] (uint64) = the
+ * value of key i in the Map this context's host result describes
+ * (kmer_count_buffer / kmer_finish_device(.., out)), 0 when the key is not in
+ * it.  For an A/C/G/T key x with C[.] the table's count of a class {x, rc x}:
+ * table mode -- 0 unless x starts with the prefix, else C[class of x], doubled
+ * when x is its own reverse complement; canonical mode -- 0 unless x is the
+ * lexicographically smaller of {x, rc x} and starts with the prefix, else
+ * C[class of x].  Keys with any other byte (N, lowercase, '\r', ...) are record
+ * keys, which live on the host: kmer_table_lookup answers them from the
+ * context's records (as the host result lists them), kmer_table_lookup_device
+ * answers 0 for them.  The lookup runs on the device against the table where
+ * it lies and leaves it unchanged; it may be repeated, and interleaved with
+ * kmer_table_stats / kmer_table_digest, until the next reset.  An exchanged
+ * table (kmer_table_finish_exchanged) answers 0 for classes other ranks own,
+ * so the ranks' answers add up.
+ * kmer_table_lookup: host arrays; the keys go up in bounded pieces, so device
+ * and pinned memory do not grow with n.  On a group (ndev > 1) every child
+ * looks all keys up in its slice of the table and the answers add.
+ * kmer_table_lookup_device: d_keys (n * k bytes) and d_counts (n uint64) in
+ * device memory, single-device contexts only (KMER_E_STATE on a group); the
+ * lookup waits for the work queued so far on `stream` (hipStream_t; NULL = the
+ * legacy default stream), and d_counts is complete when the call returns.
+ * KMER_E_STATE unless a table finish holds results; KMER_E_BAD_PARAM for NULL
+ * pointers with n > 0; n == 0 is KMER_OK and touches nothing. */
+kmer_status kmer_table_lookup(kmer_ctx *ctx, const char *keys, uint64_t n, uint64_t *counts);
+kmer_status kmer_table_lookup_device(kmer_ctx *ctx, const void *d_keys, uint64_t n, void *d_counts, void *stream);
+/* The table itself, in device memory (to read counts, use kmer_table_lookup,
+ * which owns the two key encodings below; this is the raw layout for a
+ * consumer that walks the whole table).  2^20 buckets; bucket q holds
  * bucket_len[q] (uint32) entries at entries[bucket_start[q] ..] (uint64 each:
  * remainder << 20 | count, count == 0xFFFFF meaning "see the big list").
  * h = q << 44 | remainder = c * 0x9E3779B97F4A7C15 (mod 2^64), a bijection of the canonical

@@ -37,6 +37,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_synth_fastq_device",
            "kmer_last_timing", "kmer_phase_times", "kmer_table_stats", "kmer_table_digest", "kmer_table_routes", "kmer_table_device",
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
+           "kmer_table_lookup", "kmer_table_lookup_device",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
 MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_close", "kmer_match_open", "kmer_match_open_device",
@@ -127,6 +128,8 @@ def _load():
                                              ctypes.POINTER(vp), pu64]),
         "kmer_table_exchange_prepare": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(vp), pu64, pu64]),
         "kmer_table_finish_exchanged": (ctypes.c_int, [vp, vp, u64, pu64, ctypes.c_uint32, ctypes.c_uint32, vp]),
+        "kmer_table_lookup": (ctypes.c_int, [vp, ctypes.c_char_p, u64, pu64]),
+        "kmer_table_lookup_device": (ctypes.c_int, [vp, vp, u64, vp, vp]),
         "kmer_status_string": (ctypes.c_char_p, [ctypes.c_int]),
         "kmer_last_error": (ctypes.c_char_p, [vp]),
         "kmer_version": (ctypes.c_char_p, []),
@@ -391,6 +394,39 @@ class Counter:
         self._check(LIB.kmer_table_device(self.h, ctypes.byref(e), ctypes.byref(st), ctypes.byref(ln),
                                           ctypes.byref(bg), ctypes.byref(nb)), "table_device")
         return e.value or 0, st.value or 0, ln.value or 0, bg.value or 0, nb.value
+
+    def table_lookup(self, keys):
+        """Table mode, after a finish: the Map values of query keys (0: not in
+        the Map).  keys: one bytes object of n * k bytes -> a numpy uint64
+        array of n counts; or an iterable of bytes -> a list of ints (a key
+        whose length is not k answers 0 without reaching the library)."""
+        k = self.k
+        if isinstance(keys, (bytes, bytearray, memoryview)):
+            buf = bytes(keys)
+            if len(buf) % k:
+                raise ValueError("table_lookup: %d bytes are not a whole number of %d-byte keys" % (len(buf), k))
+            return self._table_lookup(buf, len(buf) // k)
+        keys = [bytes(x) for x in keys]
+        good = [i for i, x in enumerate(keys) if len(x) == k]
+        cnt = self._table_lookup(b"".join(keys[i] for i in good), len(good)).tolist()
+        out = [0] * len(keys)
+        for i, v in zip(good, cnt):
+            out[i] = v
+        return out
+
+    def _table_lookup(self, buf, n):
+        import numpy as np
+        out = np.zeros(n, dtype=np.uint64)
+        self._check(LIB.kmer_table_lookup(self.h, buf, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+                    "table_lookup")
+        return out
+
+    def table_lookup_device(self, d_keys: int, n: int, d_counts: int, stream: int = 0):
+        """kmer_table_lookup_device: n keys of k bytes at d_keys and n uint64
+        counts at d_counts, both in device memory (record keys answer 0);
+        ordered after the work queued on `stream`, complete on return."""
+        self._check(LIB.kmer_table_lookup_device(self.h, ctypes.c_void_p(d_keys), n, ctypes.c_void_p(d_counts),
+                                                 ctypes.c_void_p(stream)), "table_lookup_device")
 
     def table_exchange_prepare(self, world):
         """Table mode across ranks: (d_send, counts, parts) -- this session's

@@ -297,6 +297,9 @@ kmer_status kmer_close(kmer_ctx *c) {
     c->tstats.release();
     c->tleft.release();
     c->trecv.release();
+    c->tlk_keys.release();
+    c->tlk_cnt.release();
+    c->tlk_bad.release();
     c->gm_keys.release();
     c->gm_keys2.release();
     for (auto *b : {&c->gm_cnt, &c->gm_cnt2, &c->gm_first, &c->gm_first2, &c->gm_h1, &c->gm_h2, &c->gm_h1b, &c->gm_h2b})
@@ -813,6 +816,128 @@ kmer_status kmer_table_digest(kmer_ctx *c, uint64_t *digest) {
         acc += (b.count - TAB_CMAX) * tab_digest_mix(tab_digest_key(b.h, c->p.k, narrow));
     *digest = acc;
     return KMER_OK;
+}
+
+// ---- table lookup (kmer_lookup.hip) ----
+constexpr uint64_t LOOKUP_PIECE = 1ull << 20;   // keys per upload of the host call (<= 32 MiB of the arena)
+
+static kmer_status lookup_state(kmer_ctx *c) {
+    if (c->mode != MODE_TABLE) return fail(c, KMER_E_STATE, "not a table-mode context (KMER_FLAG_UNORDERED)");
+    if (!c->t_done) return fail(c, KMER_E_STATE, "no table finish yet");
+    return KMER_OK;
+}
+
+// The lookup of n device-resident keys, queued on the context's stream and
+// waited for; a refused bucket extent (ERR_TAB_LOOKUP) is reported here.
+static kmer_status lookup_run(kmer_ctx *c, const uint8_t *d_keys, uint64_t n, uint64_t *d_counts) {
+    hipStream_t s = c->stream;
+    if (!c->t_keys) {                                // an empty table: every answer is 0
+        HIPCHK(c, hipMemsetAsync(d_counts, 0, n * 8, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return KMER_OK;
+    }
+    if (!c->t_ent || !c->tstart.p || !c->tnd.p || !c->tbig.p) return fail(c, KMER_E_STATE, "no table finish yet");
+    HIPCHK(c, c->tlk_bad.ensure(1, s));
+    TabLookup a;
+    memset(&a, 0, sizeof(a));
+    a.keys = d_keys;
+    a.n = n;
+    a.counts = d_counts;
+    a.ent = c->t_ent;
+    a.start = c->tstart.p;
+    a.nd = c->tnd.p;
+    a.cap = c->t_keys;
+    a.big = c->tbig.p;
+    a.n_big = std::min<uint64_t>(c->t_nbig, c->tbig.cap);
+    a.k = c->p.k;
+    for (size_t i = 0; i < c->prefix.size(); ++i) {
+        const uint8_t ch = (uint8_t)c->prefix[i];
+        a.plo |= ((((uint32_t)ch >> 1) ^ ((uint32_t)ch >> 2)) & 1u) << i;
+        a.phi |= (((uint32_t)ch >> 2) & 1u) << i;
+    }
+    a.pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
+    a.canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
+    a.err = c->d_err;
+    a.badq = c->tlk_bad.p;
+    HIPCHK(c, launch_tab_lookup(a, (uint32_t)std::max(c->n_cu, 1), s));
+    uint32_t e = 0, q = 0;
+    HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&q, c->tlk_bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (e & ERR_TAB_LOOKUP) {
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)(e & ~ERR_TAB_LOOKUP), 1, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, KMER_E_DEVICE, "table lookup: the extent of bucket " + std::to_string(q) + " lies past the table");
+    }
+    return KMER_OK;
+}
+
+kmer_status kmer_table_lookup(kmer_ctx *c, const char *keys, uint64_t n, uint64_t *counts) {
+    if (!c || (n && (!keys || !counts))) return KMER_E_BAD_PARAM;
+    const uint64_t k = c->p.k;
+    if (!c->group.empty()) {                         // a group: the children's slices are disjoint, their answers add
+        if (c->mode != MODE_TABLE || !c->t_done) return fail(c, KMER_E_STATE, "no table finish on this group yet");
+        std::vector<uint64_t> part;
+        for (uint64_t n0 = 0; n0 < n; n0 += LOOKUP_PIECE) {
+            const uint64_t m = std::min(LOOKUP_PIECE, n - n0);
+            part.resize(m);
+            std::fill(counts + n0, counts + n0 + m, 0);
+            for (kmer_ctx *x : c->group) {
+                if (hipSetDevice(x->device) != hipSuccess) return KMER_E_DEVICE;
+                const kmer_status st = kmer_table_lookup(x, keys + n0 * k, m, part.data());
+                if (st) return fail(c, st, x->err);
+                for (uint64_t i = 0; i < m; ++i) counts[n0 + i] += part[i];
+            }
+        }
+        return KMER_OK;
+    }
+    SETTLE(c);
+    kmer_status st = lookup_state(c);
+    if (st || n == 0) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    hipStream_t s = c->stream;
+    for (uint64_t n0 = 0; n0 < n; n0 += LOOKUP_PIECE) {
+        const uint64_t m = std::min(LOOKUP_PIECE, n - n0);
+        HIPCHK(c, c->tlk_keys.ensure(m * k, s));
+        HIPCHK(c, c->tlk_cnt.ensure(m, s));
+        st = upload(c, c->tlk_keys.p, keys + n0 * k, m * k, s);
+        if (st) return st;
+        st = lookup_run(c, c->tlk_keys.p, m, c->tlk_cnt.p);
+        if (st) return st;
+        HIPCHK(c, hipMemcpyAsync(counts + n0, c->tlk_cnt.p, m * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (c->exotic.empty()) return KMER_OK;
+    // keys with a byte other than A/C/G/T: the record keys, as the host result lists them
+    std::unordered_map<std::string, uint64_t> rec;
+    if (c->p.flags & KMER_FLAG_CANONICAL) {
+        for (auto &kv : canonical_records(c))
+            if (kv.first.compare(0, c->prefix.size(), c->prefix) == 0) rec.emplace(kv.first, kv.second);
+    } else {
+        for (auto &kv : c->exotic) rec.emplace(kv.first, kv.second.count);
+    }
+    std::string key;
+    for (uint64_t i = 0; i < n; ++i) {
+        const char *x = keys + i * k;
+        bool acgt = true;
+        for (uint64_t j = 0; j < k && acgt; ++j) acgt = x[j] == 'A' || x[j] == 'C' || x[j] == 'G' || x[j] == 'T';
+        if (acgt) continue;
+        key.assign(x, k);
+        const auto it = rec.find(key);
+        if (it != rec.end()) counts[i] = it->second;
+    }
+    return KMER_OK;
+}
+
+kmer_status kmer_table_lookup_device(kmer_ctx *c, const void *d_keys, uint64_t n, void *d_counts, void *stream) {
+    if (!c || (n && (!d_keys || !d_counts))) return KMER_E_BAD_PARAM;
+    SETTLE(c);
+    kmer_status st = lookup_state(c);
+    if (st || n == 0) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    HIPCHK(c, hipEventRecord(c->evw, (hipStream_t)stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
+    return lookup_run(c, (const uint8_t *)d_keys, n, (uint64_t *)d_counts);
 }
 
 kmer_status kmer_table_routes(kmer_ctx *c, uint64_t *p1_fixed, uint64_t *p1_merged, uint64_t *p1_counted,

@@ -270,6 +270,9 @@ struct kmer_ctx {
     DBuf<uint64_t> tsend;          // table exchange: send runs (sessions of several chunks)
     DBuf<uint64_t> trecv;          // group table mode: the keys this child owns, received from every child
     DBuf<TabSeg> tseg;             // ... and their segment table
+    DBuf<uint8_t> tlk_keys;        // table lookup (host call): one piece of uploaded query keys ...
+    DBuf<uint64_t> tlk_cnt;        // ... and its counts
+    DBuf<uint32_t> tlk_bad;        // table lookup: a bucket whose extent was refused (ERR_TAB_LOOKUP)
     hipEvent_t tev[8] = {};        // table phase events
     // multi-device group (kmer_params.ndev > 1): one child context per device;
     // the group itself owns no device state beyond the merge buffers on

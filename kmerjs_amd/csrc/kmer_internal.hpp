@@ -67,6 +67,7 @@ enum : uint32_t {
     ERR_TAB_CAP = 1u << 11,          // table mode: a bucket past its fixed pass-2 capacity (counted route redoes it)
     ERR_BKT_CAP = 1u << 12,          // bucket finish: a run past its bucket's fixed region (counted route redoes it)
     ERR_BKT_RANK = 1u << 13,         // bucket finish: a partitioned rank past the hits (a defect)
+    ERR_TAB_LOOKUP = 1u << 14,       // table lookup: a bucket extent past the table (not read; a defect)
     // not an error: a tile without '\n' had hits, or a tile overflowed its hit
     // slots -- cross segments may be long (finish sorts the whole cross list)
     INFO_LONGSEG = 1u << 16,
@@ -570,6 +571,44 @@ __host__ __device__ inline uint64_t tab_rc_code(uint64_t code, uint32_t k) {
     const uint32_t rhi = __builtin_bitreverse32(~hi & km) >> (32 - k);
     return ((uint64_t)rhi << k) | rlo;
 }
+// Key arithmetic of a lookup (kmer_lookup.hip, kmer_table_lookup): from the
+// k bytes of a query key to the h its class has in the table.
+// the planar code of k A/C/G/T bytes (base i at bit i of each plane); false
+// when a byte is none of the four
+__host__ __device__ inline bool tab_bytes_code(const uint8_t *x, uint32_t k, uint64_t *code) {
+    uint32_t lo = 0, hi = 0, ok = 1;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t ch = x[i];
+        ok &= (uint32_t)(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        lo |= (((ch >> 1) ^ (ch >> 2)) & 1u) << i;
+        hi |= ((ch >> 2) & 1u) << i;
+    }
+    *code = ((uint64_t)hi << k) | lo;
+    return ok != 0;
+}
+// h of the class {w, rc w} from its two orientations' planar codes: wide keys
+// (k >= 22) tab_mix of the smaller code, narrow keys tab_mix_n of the key code
+__host__ __device__ inline uint64_t tab_key_h(uint64_t cf, uint64_t cr, uint32_t k) {
+    return k <= TAB_NARROW_K ? tab_mix_n(tab_canon_n(cf, cr, k)) : tab_mix(cf < cr ? cf : cr);
+}
+// key bytes -> h (and the codes of the key and of its reverse complement)
+__host__ __device__ inline bool tab_bytes_h(const uint8_t *x, uint32_t k, uint64_t *cf, uint64_t *cr, uint64_t *h) {
+    const bool ok = tab_bytes_code(x, k, cf);
+    *cr = tab_rc_code(*cf, k);
+    *h = tab_key_h(*cf, *cr, k);
+    return ok;
+}
+// x <= y as strings (A < C < G < T, base 0 first), x and y planar codes: the
+// order in which the host result names a class (build_table_result)
+__host__ __device__ inline bool tab_str_le(uint64_t x, uint64_t y, uint32_t k) {
+    const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+    const uint32_t xl = (uint32_t)x & km, xh = (uint32_t)(x >> k) & km;
+    const uint32_t yl = (uint32_t)y & km, yh = (uint32_t)(y >> k) & km;
+    const uint32_t d = (xl ^ yl) | (xh ^ yh);
+    if (!d) return true;
+    const uint32_t j = (uint32_t)__builtin_ctz(d);
+    return (((xh >> j) & 1u) * 2 + ((xl >> j) & 1u)) < (((yh >> j) & 1u) * 2 + ((yl >> j) & 1u));
+}
 // the hash the table digest weighs: tab_mix(min(code(w), code(rc w))) for every k
 __host__ __device__ inline uint64_t tab_digest_key(uint64_t h, uint32_t k, bool narrow) {
     if (!narrow) return h;
@@ -714,6 +753,24 @@ constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a
 hipError_t launch_tab_digest(const uint64_t *ent, const uint64_t *start, const uint32_t *nd, uint32_t k,
                             uint32_t narrow, unsigned long long *out,
                              hipStream_t s);
+// Batched lookup against a finished table (kmer_lookup.hip): counts[i] = the
+// Map value of the k bytes at keys + i k (0: absent, filtered, or not A/C/G/T)
+struct TabLookup {
+    const uint8_t *keys;
+    uint64_t n;
+    uint64_t *counts;
+    const uint64_t *ent;           // the table: entries, TAB_NQ + 1 bucket starts, entries per bucket
+    const uint64_t *start;
+    const uint32_t *nd;
+    uint64_t cap;                  // entries the table's buffer holds (start[TAB_NQ] is at most this)
+    const TabBig *big;
+    uint64_t n_big;
+    uint32_t k, plo, phi, pmask;   // prefix planes (base i at bit i), mask of |P| bits
+    uint32_t canonical;            // KMER_FLAG_CANONICAL: only the class's smaller string is a key, never doubled
+    unsigned int *err;             // ERR_TAB_LOOKUP ...
+    uint32_t *badq;                // ... and a bucket it was raised for
+};
+hipError_t launch_tab_lookup(const TabLookup &a, uint32_t n_cu, hipStream_t s);
 // multi-GPU table exchange: copy n segments {src offset, dst offset, length}
 // of u64 keys (one workgroup per segment, grid-strided)
 struct TabSeg {
