@@ -29,8 +29,7 @@ const char *kmer_last_error(const kmer_ctx *ctx) { return ctx ? ctx->err.c_str()
 kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
     if (!pp || !out) return KMER_E_BAD_PARAM;
     if (pp->k == 0 || pp->step == 0 || (pp->prefix_len && !pp->prefix)) return KMER_E_BAD_PARAM;
-    // reserved / experiment-only flag bits (KMERHIP_XFLAG_*, a -DKMERHIP_EXPERIMENTS build)
-    if (!KH_EXPERIMENTS && (pp->flags & ~KMER_FLAGS_PUBLIC)) return KMER_E_BAD_PARAM;
+    if (pp->flags & ~KMER_FLAGS_PUBLIC) return KMER_E_BAD_PARAM;   // reserved flag bits
     *out = nullptr;
     if (pp->ndev > 1) {
         if (pp->ndev > 64) return KMER_E_BAD_PARAM;
@@ -56,8 +55,7 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
         // peer access between every pair of distinct devices, so the group's
         // partial / key copies (hipMemcpyPeerAsync, kmer_group.hip) go device to
         // device over xGMI.  A pair the platform refuses (no P2P path) keeps
-        // working: the runtime stages such peer copies through host memory;
-        // g->peer_staged counts those pairs (KMERHIP_PEER_LOG prints them).
+        // working: the runtime stages such peer copies through host memory.
         for (kmer_ctx *a : g->group)
             for (kmer_ctx *b : g->group) {
                 if (a->device == b->device) continue;
@@ -71,13 +69,7 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
                         e = hipSuccess;
                     }
                 }
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    ++g->peer_staged;
-                    if (getenv("KMERHIP_PEER_LOG"))
-                        fprintf(stderr, "kmerhip: no peer access %d -> %d (%s): peer copies staged by the runtime\n",
-                                a->device, b->device, hipGetErrorString(e));
-                }
+                if (e != hipSuccess) (void)hipGetLastError();
             }
         g->device = g->group[0]->device;
         g->mode = g->group[0]->mode;
@@ -107,14 +99,10 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
     if (hipSetDevice(c->device) != hipSuccess) return cleanup(KMER_E_DEVICE);
     if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) c->n_cu = 256;
     {
-        // two priorities: another session's finish (short, latency-bound
-        // kernels) is dispatched ahead of the remaining workgroups of a
-        // running scan instead of queueing behind all of them
+        // the session's one stream, at the device's highest priority
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
-        if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->sstream, hipStreamNonBlocking, lo) != hipSuccess ||
-            hipEventCreateWithFlags(&c->evq, hipEventDisableTiming) != hipSuccess)
+        if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi) != hipSuccess)
             return cleanup(KMER_E_DEVICE);
     }
 
@@ -202,11 +190,6 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
         ok &= hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0;
         c->clock_khz = khz;
     }
-    if (const char *e = exp_env("KMERHIP_TIMING"))     // (A/B experiments: events = as before, none = no records)
-        c->tmode = strcmp(e, "events") == 0 ? kmer_ctx::TIME_EVENTS
-                   : strcmp(e, "none") == 0 ? kmer_ctx::TIME_NONE : kmer_ctx::TIME_STAMPS;
-    if (const char *e = exp_env("KMERHIP_BKT_ROUTE"))  // (counted: the three-kernel partition from the start)
-        c->bkt_counted = strcmp(e, "counted") == 0;
     ok &= dalloc(&c->d_pos, 1) == hipSuccess;
     ok &= dalloc(&c->d_pos_saved, 1) == hipSuccess;
     ok &= hipHostMalloc((void **)&c->h_small, 24 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
@@ -218,7 +201,6 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
     for (hipEvent_t &e : c->fa_ev) ok &= hipEventCreate(&e) == hipSuccess;
     ok &= hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
           hipEventCreate(&c->ev2) == hipSuccess && hipEventCreate(&c->ev3) == hipSuccess &&
-          hipEventCreate(&c->ev4) == hipSuccess &&
           hipEventCreateWithFlags(&c->evw, hipEventDisableTiming) == hipSuccess;
     if (!ok) return cleanup(KMER_E_OOM);
     if (ensure_records(c, 1 << 16) || ensure_tiles(c, 1 << 12)) return cleanup(KMER_E_OOM);
@@ -312,16 +294,13 @@ kmer_status kmer_close(kmer_ctx *c) {
     if (c->h_tail) (void)hipHostFree(c->h_tail);
     for (hipStream_t us : c->up_streams) (void)hipStreamSynchronize(us);
     if (c->up_p) (void)hipHostFree(c->up_p);
-    for (hipEvent_t e : {c->ev0, c->ev1, c->ev2, c->ev3, c->ev4, c->evw})
+    for (hipEvent_t e : {c->ev0, c->ev1, c->ev2, c->ev3, c->evw})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->tev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->fa_ev)
         if (e) (void)hipEventDestroy(e);
-    if (c->sstream) (void)hipStreamSynchronize(c->sstream);
-    if (c->evq) (void)hipEventDestroy(c->evq);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->sstream) (void)hipStreamDestroy(c->sstream);
     delete c;
     return KMER_OK;
 }
@@ -995,8 +974,10 @@ kmer_status kmer_last_timing(kmer_ctx *c, double *scan_ms, double *feed_ms, doub
     if (!c) return KMER_E_BAD_PARAM;
     SETTLE(c);
     // (the finish is waited for only when its time is asked for)
-    kmer_status st = finish_ms ? resolve_out(c) : resolve_feed_timing(c);
-    if (st) return st;
+    if (finish_ms) {
+        const kmer_status st = resolve_out(c);
+        if (st) return st;
+    }
     if (scan_ms) *scan_ms = c->scan_ms;
     if (feed_ms) *feed_ms = c->feed_ms;
     if (finish_ms) *finish_ms = c->finish_ms;

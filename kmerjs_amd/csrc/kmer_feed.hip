@@ -119,33 +119,17 @@ kmer_status wait_tail(kmer_ctx *c, uint64_t seq, hipStream_t qs) {
 // The scan / feed times of the chunk whose tail was just read: its device
 // clock stamps came with the counters (no event on the chunk's stream).
 static void take_chunk_stamps(kmer_ctx *c) {
-    if (c->tmode != kmer_ctx::TIME_STAMPS) return;
     const uint64_t t0 = c->h_tail[TAIL_STAMP + STAMP_SCAN_START], t1 = c->h_tail[TAIL_STAMP + STAMP_SCAN_END],
                    t2 = c->h_tail[TAIL_STAMP + STAMP_FEED_END];
     c->scan_ms += (double)(int64_t)(t1 - t0) / c->clock_khz;
     c->feed_ms += (double)(int64_t)(t2 - t0) / c->clock_khz;
 }
 
-// Read the scan / feed kernel times of the last chunk (lazily: the chunk's
-// host wait returns before its closing event).  Event timing only.
-kmer_status resolve_feed_timing(kmer_ctx *c) {
-    if (!c->feed_timing_pending) return KMER_OK;
-    float ms = 0.f, ms_all = 0.f;
-    HIPCHK(c, hipEventSynchronize(c->ev4));
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    HIPCHK(c, hipEventElapsedTime(&ms_all, c->ev0, c->ev4));
-    c->scan_ms += ms;
-    c->feed_ms += ms_all;
-    c->feed_timing_pending = false;
-    return KMER_OK;
-}
-
 // Apply a pending reset / set_position (and `extra` PREP_* work) on the device.
 kmer_status flush_prep(kmer_ctx *c, hipStream_t s, uint32_t extra) {
     const uint32_t f = c->prep_flags | extra;
     if (!f) return KMER_OK;
-    HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, f, c->prep_lines,
-                          c->tmode == kmer_ctx::TIME_STAMPS ? c->d_stamp : nullptr, s));
+    HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, f, c->prep_lines, c->d_stamp, s));
     c->prep_flags = 0;
     return KMER_OK;
 }
@@ -217,13 +201,10 @@ kmer_status launch_chunk(kmer_ctx *c) {
     const hipStream_t s = p.s;
     // (phase times: clock stamps by the prologue, the tile reduce and the
     // chunk tail -- the stream stood idle at every event record between two
-    // launches; KMERHIP_TIMING=events: as before, A/B experiments)
-    const bool events = c->tmode == kmer_ctx::TIME_EVENTS;
-    uint64_t *stamp = c->tmode == kmer_ctx::TIME_STAMPS ? c->d_stamp : nullptr;
-    if (events) HIPCHK(c, hipEventRecord(c->ev0, s));
+    // launches)
+    uint64_t *stamp = c->d_stamp;
     if (c->planes) HIPCHK(c, launch_scan_planes(p.a, c->pargs, s));
     else HIPCHK(c, launch_scan_tiles(p.a, s));
-    if (events) HIPCHK(c, hipEventRecord(c->ev1, s));
     HIPCHK(c, launch_tile_reduce(c->tsum.p, p.n_tiles, c->bsum.p, stamp, s));
     if (p.n_blocks > TSCAN_INLINE_MAX) {
         TileSum zero;
@@ -236,12 +217,10 @@ kmer_status launch_chunk(kmer_ctx *c) {
     p.h.seq = ++c->tail_seq;
     p.h.stamp = stamp;
     HIPCHK(c, launch_hits(p.h, s));          // (+ the chunk tail: position, counters, stamps -> h_tail)
-    if (events) HIPCHK(c, hipEventRecord(c->ev4, s));
     if (s != c->stream) {                        // later work follows the chunk
         HIPCHK(c, hipEventRecord(c->evw, s));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
     }
-    c->feed_timing_pending = events;
     return KMER_OK;
 }
 
@@ -278,7 +257,6 @@ kmer_status scan_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_ti
     a.ovf_count = c->d_ovf_count;
     a.ovf_cap = c->ovf.cap;
     a.err = c->d_err;
-    a.ablate = KH_EXPERIMENTS ? (c->p.flags & KMERHIP_XFLAG_MASK) >> 8 : 0u;   // (experiments only)
     a.hits_hi = c->hits_hi.p;
     a.ovf_hi = c->ovf_hi.p;
 
@@ -302,7 +280,6 @@ kmer_status scan_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_ti
     h.hits_hi = c->hits_hi.p;
     h.ovf_hi = c->ovf_hi.p;
     h.wide = c->wide ? 1u : 0u;
-    h.ablate = a.ablate;
     if (c->wide) {                               // (high word: kbits - 64 < 64 bits, then the invalid bit)
         h.smask_hi = (1ull << (c->kbits - 64)) - 1ull;
         h.invalid_key = 1ull << (c->kbits - 64);
@@ -333,20 +310,9 @@ kmer_status scan_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_ti
     // feeds), after everything queued so far: no cross-stream event waits
     // between the previous finish, the chunk and its finish (C2: 1.009 ->
     // 0.981 ms per step; two sessions in rotation still overlap, one's finish
-    // with the other's chunk).  KMERHIP_ONE_STREAM=0: the chunk on a separate
-    // low-priority stream (A/B experiments)
-    static const bool one_stream = [] {
-        const char *e = exp_env("KMERHIP_ONE_STREAM");
-        return !(e && strcmp(e, "0") == 0);
-    }();
-    p.s = one_stream ? s : c->sstream;
-    if (p.s != s) {
-        HIPCHK(c, hipEventRecord(c->evq, s));
-        HIPCHK(c, hipStreamWaitEvent(p.s, c->evq, 0));
-    }
+    // with the other's chunk).
+    p.s = s;
     // prologue: pending reset / position, position snapshot, zeroed chunk counters
-    st = resolve_feed_timing(c);
-    if (st) return st;
     st = flush_prep(c, p.s, PREP_SAVE | PREP_ZERO);
     if (st) return st;
     p.active = true;
@@ -375,8 +341,6 @@ kmer_status settle(kmer_ctx *c) {
         if (st) return st;
         if (!(e & (ERR_OVF_OVERFLOW | ERR_REC_OVERFLOW | ERR_CROSS_OVERFLOW))) break;
         if (attempt == 7) return fail(c, KMER_E_OOM, "hit lists kept overflowing");
-        st = resolve_feed_timing(c);
-        if (st) return st;
         HIPCHK(c, hipMemsetAsync(c->d_err, 0, 4, s));
         HIPCHK(c, hipMemcpyAsync(c->d_pos, c->d_pos_saved, sizeof(StreamPos), hipMemcpyDeviceToDevice, s));
         if (e & ERR_OVF_OVERFLOW) {
@@ -404,8 +368,7 @@ kmer_status settle(kmer_ctx *c) {
         }
         bind_hits(c, p.h);
         HIPCHK(c, hipMemsetAsync(c->d_scal, 0, 3 * 8, s));   // rec, ovf, cross counts of this chunk
-        if (c->tmode == kmer_ctx::TIME_STAMPS)               // (the redo's scan start)
-            HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, 0, 0, c->d_stamp, s));
+        HIPCHK(c, launch_prep(c->d_pos, c->d_pos_saved, c->d_err, c->d_scal, 0, 0, c->d_stamp, s));   // (the redo's scan start)
         st = launch_chunk(c);
         if (st) return st;
     }
@@ -673,19 +636,10 @@ kmer_status chunk_lines(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_
                         uint64_t *n_nl_out, uint64_t *n_seq_out) {
     const uint64_t li0 = c->host_lines;
     // one pass over the input: per-tile counts + positions in per-tile slots
-    // (KMERHIP_NL=two: the count pass + a second, writing pass; A/B experiments)
-    static const bool two = [] {
-        const char *e = exp_env("KMERHIP_NL");
-        return e && strcmp(e, "two") == 0;
-    }();
     HIPCHK(c, c->tcount.ensure(n_tiles, s));
     HIPCHK(c, c->tbase.ensure(n_tiles, s));
-    if (two) {
-        HIPCHK(c, launch_nl_count(d, len, n_tiles, c->tcount.p, c->d_err, s));
-    } else {
-        HIPCHK(c, c->nlslots.ensure((uint64_t)n_tiles * NL_SLOTS, s));
-        HIPCHK(c, launch_nl_slots(d, len, n_tiles, NL_SLOTS, c->nlslots.p, c->tcount.p, c->d_err, s));
-    }
+    HIPCHK(c, c->nlslots.ensure((uint64_t)n_tiles * NL_SLOTS, s));
+    HIPCHK(c, launch_nl_slots(d, len, n_tiles, NL_SLOTS, c->nlslots.p, c->tcount.p, c->d_err, s));
     ROCPRIM_RUN(c, rocprim::exclusive_scan(t, b, c->tcount.p, c->tbase.p, (uint64_t)0, (size_t)n_tiles,
                                            rocprim::plus<uint64_t>(), s));
     HIPCHK(c, hipMemcpyAsync(c->h_small + 14, c->tbase.p + n_tiles - 1, 8, hipMemcpyDeviceToHost, s));
@@ -695,7 +649,7 @@ kmer_status chunk_lines(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_
     const uint32_t e = (uint32_t)c->h_small[5];
     kmer_status st = check_err(c, e);
     if (st) return st;
-    const bool slots = !two && !(e & ERR_LINE_OVERFLOW);
+    const bool slots = !(e & ERR_LINE_OVERFLOW);
     if (e & ERR_LINE_OVERFLOW)                   // (short lines: two passes; other bits kept)
         HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)(e & ~ERR_LINE_OVERFLOW), 1, s));
     const uint64_t n_nl = c->h_small[14] + (uint32_t)c->h_small[15];
@@ -832,8 +786,8 @@ kmer_status dense_windows_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint
 // Dense-hit path: every window of every sequence line goes to its rank slot
 // (step > 1; no prefix, where every ACGT window is accepted and the count
 // pass would only repeat the line lengths: k 21 / 4 M reads 78.1 vs 97.0 ms,
-// C5 ordered 78.9 vs 95.4 ms, profiles/r06_ab/dense_*; and KMERHIP_DENSE=slots
-// in experiment builds); with a prefix (step 1), and always past k = 32, only
+// C5 ordered 78.9 vs 95.4 ms, profiles/r06_ab/dense_*);
+// with a prefix (step 1), and always past k = 32, only
 // the accepted windows are ranked (dense_windows_feed: k 16 / AT 15.6 vs 33.3 ms).
 kmer_status windows_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_tiles, hipStream_t s) {
     const uint64_t li0 = c->host_lines;
@@ -842,11 +796,7 @@ kmer_status windows_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n
     uint64_t n_nl = 0, n_seq = 0;
     st = chunk_lines(c, d, len, n_tiles, s, true, &n_nl, &n_seq);
     if (st) return st;
-    static const bool slots_only = [] {
-        const char *e = exp_env("KMERHIP_DENSE");
-        return e && strcmp(e, "slots") == 0;
-    }();
-    if (c->p.step == 1 && (c->p.k > (uint32_t)KMAX_DENSE || (!slots_only && !c->prefix.empty())))
+    if (c->p.step == 1 && (c->p.k > (uint32_t)KMAX_DENSE || !c->prefix.empty()))
         return dense_windows_feed(c, d, len, n_seq, n_nl, li0, s);
     c->win_slots = true;                          // (the finish compacts the rejected windows' slots away)
     uint64_t total = 0;
@@ -1012,7 +962,6 @@ kmer_status feed(kmer_ctx *c, const uint8_t *d, uint64_t len, hipStream_t s) {
 kmer_status reset(kmer_ctx *c) {
     (void)settle(c);                             // (a chunk abandoned by the reset: its errors do not matter)
     c->prep_flags = PREP_RESET;
-    c->feed_timing_pending = false;
     c->exotic.clear();
     c->abs_offset = 0;
     c->n_hits = 0;

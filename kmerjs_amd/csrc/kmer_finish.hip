@@ -186,7 +186,6 @@ static kmer_status bucket_observe(kmer_ctx *c, bool *redo) {
     const uint32_t e = (uint32_t)c->h_tail[TAIL_ERR];
     if (e & ERR_BKT_RANK) return check_err(c, e);
     if (e & ERR_BKT_CAP) {
-        if (exp_env("KMERHIP_BKT_LOG")) fprintf(stderr, "bucket finish: a bucket past its region, counted route\n");
         c->bkt_counted = true;
         *redo = true;
     }
@@ -195,14 +194,12 @@ static kmer_status bucket_observe(kmer_ctx *c, bool *redo) {
 
 // resolve a deferred unique count (finish without a host result)
 kmer_status resolve_out(kmer_ctx *c) {
-    kmer_status st = resolve_feed_timing(c);
-    if (st) return st;
     if (c->out_pending) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->n_out = c->h_tail[TAIL_NUNIQ];
         c->out_pending = false;
         bool redo = false;
-        st = bucket_observe(c, &redo);
+        kmer_status st = bucket_observe(c, &redo);
         if (st) return st;
         if (redo) {                              // (the rank arrays are as the finish left them)
             uint64_t nu = 0;
@@ -569,9 +566,8 @@ kmer_status finish(kmer_ctx *c, kmer_result **out) {
     // kernel (cross_segsort, or the partition) stamps the start, the emit the
     // end, and nothing but launches touches the stream after the chunk's tail.
     // Every other finish keeps its events.
-    const bool stamped = c->tmode == kmer_ctx::TIME_STAMPS && c->mode == MODE_PACKED && c->n_hits > 0 &&
-                         bucket_route(c, false) && !(c->n_cross && c->long_seg);
-    const bool events = !stamped && c->tmode != kmer_ctx::TIME_NONE;
+    const bool stamped = c->mode == MODE_PACKED && c->n_hits > 0 && bucket_route(c, false) && !(c->n_cross && c->long_seg);
+    const bool events = !stamped;
     c->fin_stamp = c->fin_emit = stamped ? c->d_stamp : nullptr;
     if (events) HIPCHK(c, hipEventRecord(c->ev2, c->stream));
     uint64_t nu = 0;

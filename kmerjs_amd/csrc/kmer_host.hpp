@@ -90,10 +90,6 @@ struct DBuf {
         T *q = nullptr;
         e = hipMalloc((void **)&q, nc * sizeof(T));
         if (e != hipSuccess) return e;
-        if (exp_env("KMERHIP_POISON")) {           // (experiments build: every new buffer starts as 0xA5 bytes)
-            e = hipMemsetAsync(q, 0xA5, nc * sizeof(T), s);
-            if (e != hipSuccess) return e;
-        }
         if (p) {
             if (keep && used) {
                 e = hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, s);
@@ -132,9 +128,7 @@ struct kmer_ctx {
     Mode mode = MODE_GENERAL;
     int device = 0;
     uint32_t pbits = PBITS_DEFAULT;       // order-key position bits (PBITS_LONG: long-line mode)
-    hipStream_t stream = nullptr;  // high priority: finish, exchange, copies, everything but the scan chain
-    hipStream_t sstream = nullptr; // low priority: a packed-path chunk (scan, tile scan, hit resolution)
-    hipEvent_t evq = nullptr;      // orders sstream after stream
+    hipStream_t stream = nullptr;  // the session's one stream (highest priority)
     std::string err;
     uint32_t kbits = 0;            // packed key bits = 2*(k - |P|)
     bool wide = false;             // packed keys of >= 64 bits (k <= 64): two words, the high one in rkeyh
@@ -229,7 +223,6 @@ struct kmer_ctx {
     uint64_t *d_tail = nullptr;    // ... its device address
     unsigned int *d_hticket = nullptr;   // chunk tail last-block ticket (d_scal[8])
     uint64_t tail_seq = 0;         // last chunk sequence number handed to the chunk tail kernel
-    bool feed_timing_pending = false;   // scan / feed events of the last chunk not yet read
     uint32_t prep_flags = 0;       // PREP_RESET / PREP_SETPOS pending for the next feed's prologue
     // the last packed-path chunk, launched but not yet settled (its tail read,
     // overflows redone, counters applied): settle() before any other use
@@ -278,7 +271,6 @@ struct kmer_ctx {
     // the group itself owns no device state beyond the merge buffers on
     // devices[0] (allocated through child 0)
     std::vector<kmer_ctx *> group;
-    uint32_t peer_staged = 0;      // device pairs of the group without peer access (copies staged by the runtime)
     // general path, device merge (step 1, kmer_finish.hip general_merge):
     // session entries -- key bytes at stride k, counts, first-occurrence keys
     bool gm_on = false;
@@ -297,13 +289,12 @@ struct kmer_ctx {
     // timing: the packed path's chunk and bucket finish by device clock stamps
     // (no event between the launches of a step); every other path by HIP
     // events on the context stream
-    enum { TIME_STAMPS, TIME_EVENTS, TIME_NONE } tmode = TIME_STAMPS;   // (experiments: KMERHIP_TIMING)
     uint64_t *d_stamp = nullptr;   // STAMP_* words
     double clock_khz = 0.0;        // rate of wall_clock64 (hipDeviceAttributeWallClockRate)
     uint64_t *fin_stamp = nullptr; // finish(): handed to the first kernel of the finish (it stamps STAMP_FINISH_START)
     uint64_t *fin_emit = nullptr;  // ... and to the emit (finish start / end -> h_tail)
     bool finish_stamped = false;   // the pending finish time is in h_tail's stamps, not in ev2 / ev3
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, ev4 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     hipEvent_t evw = nullptr;      // cross-stream wait (no timing)
     double scan_ms = 0.0, feed_ms = 0.0, finish_ms = 0.0;
     // FASTA input (KMER_FLAG_FASTA, kmer_fasta.hip): each chunk is rewritten
@@ -417,7 +408,6 @@ kmer_status ensure_ovf(kmer_ctx *c, uint64_t n, hipStream_t s);
 kmer_status ensure_records(kmer_ctx *c, uint64_t n);
 kmer_status drain_records(kmer_ctx *c, const uint8_t *d_data, uint64_t n, hipStream_t s);
 kmer_status wait_tail(kmer_ctx *c, uint64_t seq, hipStream_t qs);
-kmer_status resolve_feed_timing(kmer_ctx *c);
 bool bucket_route(const kmer_ctx *c, bool with_counts);
 kmer_status flush_prep(kmer_ctx *c, hipStream_t s, uint32_t extra);
 kmer_status check_err(kmer_ctx *c, uint32_t e);

@@ -4,30 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace kmerhip {
 
-// ---- experiment switches ----------------------------------------------------
-// A/B switches (KMERHIP_* environment variables) and ablations (the
-// KMERHIP_XFLAG_ABLATE_* bits of kmer_params.flags; results are WRONG with
-// them) exist only in a -DKMERHIP_EXPERIMENTS build of the library, made by
-// tools/ for timing studies.  The shipping libkmerhip.so reads no environment
-// variable, and kmer_open rejects the ablation bits (KMER_E_BAD_PARAM).
-#ifdef KMERHIP_EXPERIMENTS
-inline const char *exp_env(const char *name) { return getenv(name); }
-#define KH_ABLATE(a) ((a).ablate)
-constexpr bool KH_EXPERIMENTS = true;
-#else
-inline const char *exp_env(const char *) { return nullptr; }
-#define KH_ABLATE(a) 0u
-constexpr bool KH_EXPERIMENTS = false;
-#endif
-enum : uint32_t {
-    KMERHIP_XFLAG_ABLATE_HITS = 1u << 8,   // drop every prefix candidate
-    KMERHIP_XFLAG_ABLATE_SWAR = 1u << 9,   // skip the SWAR prefix scan
-    KMERHIP_XFLAG_MASK = 0xFFu << 8,       // bits 8..15: tile-scan ablations (ScanArgs::ablate)
-};
+// The library reads no environment variable.
 
 // ---- tile geometry (tile kernel) -------------------------------------------
 // One workgroup owns one 16 KiB tile of the input.  The tile plus a front halo
@@ -150,7 +130,6 @@ struct ScanArgs {
     unsigned long long *ovf_count;
     uint64_t ovf_cap;
     unsigned int *err;
-    uint32_t ablate;               // experiments only: bit0 = drop all candidates
     uint64_t *hits_hi, *ovf_hi;    // k > 32: code of the window's first k - 32 bases, per hit slot
 };
 
@@ -192,7 +171,6 @@ struct HitArgs {
     // holds the entry's own index until apply_cross has moved it)
     const uint64_t *hits_hi, *ovf_hi;
     uint32_t wide;
-    uint32_t ablate;               // experiments (KMER_FLAG_ABLATE_*): no line-length errors on unwritten records
     uint64_t smask_hi;             // wide: mask of the high word (2(k - |P|) - 64 bits)
     uint64_t *rkeyh;
     uint64_t *xkeyh, *xkeyl;
@@ -482,8 +460,6 @@ hipError_t launch_merge_prep(const uint64_t *keys, const Agg *vals, uint64_t n, 
                              uint64_t *rord, uint64_t *rcnt, uint32_t *ridx, hipStream_t s);
 hipError_t launch_gather_records(const Record *recs, uint64_t stride, uint64_t n,
                                  const uint8_t *data, uint8_t *out, hipStream_t s);
-hipError_t launch_nl_count(const uint8_t *data, uint64_t len, uint32_t n_tiles, uint32_t *tcount, unsigned int *err,
-                           hipStream_t s);
 hipError_t launch_nl_write(const uint8_t *data, uint64_t len, uint32_t n_tiles, const uint64_t *tbase, uint64_t *nl,
                            hipStream_t s);
 // one pass: per-tile '\n' counts + tile-relative positions in `cap` u16 slots per
@@ -675,8 +651,6 @@ struct TabFinal {
     uint32_t sub_bits;             // (unused: ranges are sized per unit from range_keys)
     uint32_t range_keys;           // target keys per LDS range (small buckets are grouped up to it)
     uint32_t cap;                  // claims per range before it is split (<= TAB_CAP)
-    uint32_t ablate;               // experiments only (results WRONG): 1 no insert, 2 no emit; sort kernel:
-                                   // 8 no bin scan, 16 no statistics, 32 no entry stores
     TabBig *big;
     unsigned long long *big_count;
     uint64_t big_cap;
@@ -687,7 +661,6 @@ struct TabFinal {
     uint32_t narrow;               // keys h = tab_mix_n(c) (k <= 21)
     uint32_t b2n;                  // (narrow, capq) B2 holds 32-bit keys: (uint32_t)(h >> 23) (bucket offset, remainder)
     unsigned long long *stats;     // [0] canonical entries [1] Map keys [2] sum of Map counts
-    uint64_t *prof;                // experiments only (KMERHIP_TAB_PROF): per-workgroup phase clocks, 8 each
     uint32_t qlo, qhi;             // buckets [qlo, qhi) of this table (multi-GPU: the rank's partitions)
     // units the sort kernel (tab_sort_final) leaves to the general kernel: pairs
     // [q, qe) of buckets; the general kernel walks this list instead of

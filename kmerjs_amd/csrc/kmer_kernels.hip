@@ -554,10 +554,6 @@ __device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, 
     // not a prefix hit after all; crosses a line end (or the end of input); k == 1: line.length > 1
     const bool valid = pfx_bits == 0 && !hasnl &&
                        !(k == 1 && buf[FH + s0 - 1] == '\n' && buf[FH + s0 + 1] == '\n');
-    if (THREAD_MAP && (KH_ABLATE(a) & 4u)) {     // experiments: verified, no record
-        if (valid) atomicAdd(&sh.nx, 0u);
-        return;
-    }
     // tile-local line context of the window start: '\n' count before s0 and
     // the start of its line if that lies inside this tile
     uint32_t c_local = 0;
@@ -671,7 +667,6 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
     uint64_t packed = 0;         // 16-bit '\n' count of chunk i in bits [16i, 16i+16)
     // only the last tile has bytes past len (sentinels): keep the masking out of the hot loop
     const bool tail_tile = (uint64_t)(g0 + TILE) > len;
-    const bool do_swar = !(KH_ABLATE(a) & 2u);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = tid + TPB * i;
@@ -686,26 +681,24 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) cnt += __popc(nl_flags_below(x[j], (int64_t)len - (gc + 4 * j)));
         }
-        if (do_swar) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                // 4-byte windows at the word's 4 positions vs P[0:4] / rc(P)[0:4]:
-                // xor + min on the vector unit (the compare-and-OR form would
-                // load the scalar unit, which this kernel is short of)
-                const uint32_t x0 = x[j];
-                const uint32_t x1 = align4(x[j + 1], x[j], 1);
-                const uint32_t x2 = align4(x[j + 1], x[j], 2);
-                const uint32_t x3 = align4(x[j + 1], x[j], 3);
-                uint32_t m;
-                if (FULL4) {
-                    m = min(min(min(x0 ^ P4, x1 ^ P4), min(x2 ^ P4, x3 ^ P4)),
-                            min(min(x0 ^ R4, x1 ^ R4), min(x2 ^ R4, x3 ^ R4)));
-                } else {
-                    m = min(min(min((x0 ^ P4) & PM, (x1 ^ P4) & PM), min((x2 ^ P4) & PM, (x3 ^ P4) & PM)),
-                            min(min((x0 ^ R4) & PM, (x1 ^ R4) & PM), min((x2 ^ R4) & PM, (x3 ^ R4) & PM)));
-                }
-                cand |= m == 0 ? (1u << (4 * i + j)) : 0u;
+        for (int j = 0; j < 4; ++j) {
+            // 4-byte windows at the word's 4 positions vs P[0:4] / rc(P)[0:4]:
+            // xor + min on the vector unit (the compare-and-OR form would
+            // load the scalar unit, which this kernel is short of)
+            const uint32_t x0 = x[j];
+            const uint32_t x1 = align4(x[j + 1], x[j], 1);
+            const uint32_t x2 = align4(x[j + 1], x[j], 2);
+            const uint32_t x3 = align4(x[j + 1], x[j], 3);
+            uint32_t m;
+            if (FULL4) {
+                m = min(min(min(x0 ^ P4, x1 ^ P4), min(x2 ^ P4, x3 ^ P4)),
+                        min(min(x0 ^ R4, x1 ^ R4), min(x2 ^ R4, x3 ^ R4)));
+            } else {
+                m = min(min(min((x0 ^ P4) & PM, (x1 ^ P4) & PM), min((x2 ^ P4) & PM, (x3 ^ P4) & PM)),
+                        min(min((x0 ^ R4) & PM, (x1 ^ R4) & PM), min((x2 ^ R4) & PM, (x3 ^ R4) & PM)));
             }
+            cand |= m == 0 ? (1u << (4 * i + j)) : 0u;
         }
         packed |= (uint64_t)cnt << (16 * i);
         // chunk bitmap + highest chunk with a '\n', from one ballot (no per-lane atomics)
@@ -759,7 +752,7 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
         a.tsum[tile].lnl = lp >= 0 ? a.abs_offset + (uint64_t)(g0 + lp + 1) : 0;
     }
     const uint32_t k = a.k, plen = a.plen;
-    if (plen > k || (KH_ABLATE(a) & 1u)) cand = 0;
+    if (plen > k) cand = 0;
     const uint32_t *pw = (const uint32_t *)s_pr;             // P words, then rc(P) words
 
     // ---- candidate words -> LDS queue (one LDS atomic per wave) -> verified
@@ -953,7 +946,7 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
         mf[h] = plane_match(L[h], H[h], L[h + 1], H[h + 1], kl, kh, pb, SL, SH);
         mr[h] = plane_match(L[h], H[h], L[h + 1], H[h + 1], rl, rh, pb, SL, SH);
     }
-    if ((!K && a.k < a.plen) || (KH_ABLATE(a) & 1u)) mf[0] = mf[1] = mr[0] = mr[1] = 0;
+    if (!K && a.k < a.plen) mf[0] = mf[1] = mr[0] = mr[1] = 0;
 
     // ---- block scan of the per-thread '\\n' counts -> cpre per chunk ----
     __syncthreads();
@@ -1091,10 +1084,10 @@ __device__ __forceinline__ uint64_t resolve_hit(const HitArgs &a, uint64_t pos_l
     const bool seq = (li & 3) == 1;
     const uint64_t maxrel = (1ull << a.pbits) - 1ull;
     if (rel > maxrel) {
-        if (seq && !KH_ABLATE(a)) atomicOr(a.err, ERR_LINE_TOO_LONG);
+        if (seq) atomicOr(a.err, ERR_LINE_TOO_LONG);
         rel = maxrel;                            // (non-sequence lines only need a consistent order)
     }
-    if ((li >> (63 - a.pbits)) && !KH_ABLATE(a)) atomicOr(a.err, ERR_LINE_TOO_LONG);   // (line field full: long-line mode)
+    if (li >> (63 - a.pbits)) atomicOr(a.err, ERR_LINE_TOO_LONG);   // (line field full: long-line mode)
     const uint64_t order = (li << (a.pbits + 1)) | ((uint64_t)strand << a.pbits) | (strand ? maxrel - rel : rel);
     *order_out = order;
     const uint32_t sp = (uint32_t)(s0 + 64);     // < 2^15
@@ -2131,19 +2124,6 @@ __device__ __forceinline__ uint32_t thread_nl_flags(const uint8_t *data, uint64_
     for (int j = 0; j < 16; ++j) cnt += __popc(z[j]);
     *orall = o;
     return cnt;
-}
-
-__global__ __launch_bounds__(256) void nl_count_kernel(const uint8_t *data, uint64_t len, uint32_t *tcount,
-                                                       unsigned int *err) {
-    __shared__ uint32_t ws[4];
-    uint32_t z[16], o = 0;
-    const int64_t g = (int64_t)blockIdx.x * TILE + 64 * threadIdx.x;
-    const uint32_t cnt = (uint64_t)g < len ? thread_nl_flags(data, len, g, z, &o) : 0u;
-    if (o & 0x80808080u) atomicOr(err, ERR_NONASCII);
-    const uint32_t incl = wave_incl_sum(cnt);
-    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) tcount[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
 __global__ __launch_bounds__(256) void nl_write_kernel(const uint8_t *data, uint64_t len, const uint64_t *tbase,
@@ -3730,11 +3710,6 @@ hipError_t launch_gather_records(const Record *recs, uint64_t stride, uint64_t n
     return hipGetLastError();
 }
 
-hipError_t launch_nl_count(const uint8_t *data, uint64_t len, uint32_t n_tiles, uint32_t *tcount, unsigned int *err,
-                           hipStream_t s) {
-    hipLaunchKernelGGL(nl_count_kernel, dim3(n_tiles), dim3(256), 0, s, data, len, tcount, err);
-    return hipGetLastError();
-}
 hipError_t launch_nl_write(const uint8_t *data, uint64_t len, uint32_t n_tiles, const uint64_t *tbase, uint64_t *nl,
                            hipStream_t s) {
     hipLaunchKernelGGL(nl_write_kernel, dim3(n_tiles), dim3(256), 0, s, data, len, tbase, nl);

@@ -99,10 +99,8 @@ kmer_status table_pass1_fixed(kmer_ctx *c, TabArgs &a, hipStream_t s, bool *done
     const float ms0 = ev_ms(c, c->tev[0], c->tev[1]), ms1 = ev_ms(c, c->tev[1], c->tev[2]);
     uint64_t tot = 0;
     hp[0] = 0;
-    double sig = 2.0;                          // (KMERHIP_TAB_SIGMA: A/B experiments)
-    if (const char *e = exp_env("KMERHIP_TAB_SIGMA")) sig = atof(e);
-    uint64_t sdiv = 64;                        // spill area: R / sdiv slots (KMERHIP_TAB_SPILLDIV: A/B experiments)
-    if (const char *e = exp_env("KMERHIP_TAB_SPILLDIV")) sdiv = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    const double sig = 2.0;                    // run capacity: mean + sig standard deviations
+    const uint64_t sdiv = 64;                  // spill area: R / sdiv slots
     for (uint32_t w = 0; w < a.nwg; ++w) tot += hw[w];
     // (runs of whole 64-B blocks: 8 keys, narrow keys 16)
     const uint64_t al = a.narrow ? 16 : 8;
@@ -156,10 +154,7 @@ kmer_status table_pass1_fixed(kmer_ctx *c, TabArgs &a, hipStream_t s, bool *done
     st = table_scatter1(c, a, s, launch_tab_scatter1f);
     if (st) return st;
     const unsigned long long over = c->h_small[17];   // (read with table_scatter1's wait)
-    if (over) {                                // (records of the attempt are dropped: the counted pass redoes them)
-        if (exp_env("KMERHIP_TAB_SPILL_LOG")) fprintf(stderr, "tab pass 1: spill area overflow (%llu)\n", over);
-        return KMER_OK;
-    }
+    if (over) return KMER_OK;                  // (records of the attempt are dropped: the counted pass redoes them)
     HIPCHK(c, launch_tab_spill_fill(a.narrow != 0, c->tb1.p, cb, R, S, PS, c->tspc.p, s));
     std::vector<uint64_t> off(TAB_NB + 1);
     for (uint32_t p = 0; p <= TAB_NB; ++p) off[p] = (uint64_t)p * PS;
@@ -167,9 +162,6 @@ kmer_status table_pass1_fixed(kmer_ctx *c, TabArgs &a, hipStream_t s, bool *done
     c->t_coff.push_back(std::move(off));
     c->t_keys = cb + region;
     c->t_fill += region - std::min<uint64_t>(region, tot);
-    if (exp_env("KMERHIP_TAB_SPILL_LOG"))
-        fprintf(stderr, "tab pass 1: %llu keys, %llu slots (spill areas of %llu)\n", (unsigned long long)tot,
-                (unsigned long long)region, (unsigned long long)S);
     c->t_ms[0] += ms0;
     c->t_ms[1] += ms1;
     c->t_p1_fixed += 1;
@@ -236,8 +228,6 @@ kmer_status table_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_t
         a.pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
         a.canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
         a.narrow = c->p.k <= TAB_NARROW_K ? 1u : 0u;
-        if (const char *hx = exp_env("KMERHIP_TAB_HASH"))   // (A/B experiments: shift = no mix, results wrong)
-            if (a.narrow && strcmp(hx, "shift") == 0) a.narrow = 2;
         a.err = c->d_err;
         const uint64_t nh = (uint64_t)TAB_NB * a.nwg;
         HIPCHK(c, c->tH.ensure(nh, s));
@@ -245,10 +235,8 @@ kmer_status table_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_t
         HIPCHK(c, c->tp1.ensure(TAB_NB, s));
         // no prefix and k <= 31: pass 1 without the counting pass (fixed runs,
         // tab_scatter1f); an overfull spill list falls back to the counted pass
-        // (KMERHIP_TAB_P1=count: always counted, A/B experiments)
-        const char *p1 = exp_env("KMERHIP_TAB_P1");
         bool done = false;
-        if (a.pmask == 0 && a.k <= 31 && !(p1 && strcmp(p1, "count") == 0)) {
+        if (a.pmask == 0 && a.k <= 31) {
             st = table_pass1_fixed(c, a, s, &done);
             if (st) return st;
         }
@@ -296,10 +284,8 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     std::vector<TabUnit> heads(TAB_NB);
     std::vector<uint32_t> ufirst(TAB_NB);
     uint64_t ubase = 0;
-    // a partition's run in a chunk is cut into ceil(len / cap) units of equal
-    // length (KMERHIP_TAB_UNIT: the cap, A/B experiments)
-    uint64_t ucap = TAB_UNIT;
-    if (const char *e = exp_env("KMERHIP_TAB_UNIT")) ucap = std::max<uint64_t>(8192, strtoull(e, nullptr, 10));
+    // a partition's run in a chunk is cut into ceil(len / cap) units of equal length
+    const uint64_t ucap = TAB_UNIT;
     for (uint32_t p = 0; p < TAB_NB; ++p) {
         const size_t first = units.size();
         for (size_t ch = 0; ch < c->t_cbase.size(); ++ch) {
@@ -346,23 +332,20 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     // sort-final group (TS_CAPG keys: C5 11 buckets).  Else (small tables,
     // < 2^24 keys) or after a capacity overflow, the counted route:
     // tab_hist2, a scan, tab_scatter2c, bucket starts.
-    // KMER_FLAG_TABLE_FIXED_TEST: from any table size.  (KMERHIP_TAB_P2=count:
-    // always counted, A/B experiments.)
+    // KMER_FLAG_TABLE_FIXED_TEST: from any table size.
     const uint64_t n_est = n - std::min(n, c->t_fill);             // keys (filler slots excluded; an upper bound)
     const double mu = (double)n_est / TAB_NQ;
-    const char *p2 = exp_env("KMERHIP_TAB_P2");
     // Narrow keys (k <= 21, tab_mix_n): B2 holds 32-bit keys, and the sort
     // final takes a region of up to TAB_SORT_KEYS of them (C5: 24 buckets).
     const bool narrow = c->p.k <= TAB_NARROW_K;
     const uint64_t al = narrow ? 16 : 8;            // (64-B blocks of keys)
     auto cap6 = [&](double m) { return ((uint64_t)(m + 6.0 * std::sqrt(m)) + 16 + al - 1) & ~(al - 1); };
-    const bool sort_ok = !exp_env("KMERHIP_TAB_FINAL") && !exp_env("KMERHIP_TAB_PROF");   // (general final alone: qg 1)
     uint32_t qg = 0;
     if (mu >= 2048.0 && !narrow) {
         qg = 1;
     } else {
         const uint64_t lim = narrow ? TAB_SORT_KEYS_BIG : TAB_SORT_GROUP_KEYS;
-        for (uint32_t g = sort_ok ? 64 : 1; g >= 1 && !qg; --g)
+        for (uint32_t g = 64; g >= 1 && !qg; --g)
             if (cap6(g * mu) <= lim && (g >= 2 || narrow)) qg = g;
     }
     // (a crowded region sets ERR_TAB_CAP: the finals then do nothing, and the
@@ -373,8 +356,7 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     uint64_t capq = 0;
     uint32_t rpp = TAB_NB, gmag = 1u << 20;
     if (try_fixed && qg && (n_est >= (1ull << 24) || (c->p.flags & KMER_FLAG_TABLE_FIXED_TEST)) &&
-        !(c->p.flags & KMER_FLAG_TABLE_SPLIT_TEST) && !(p2 && strcmp(p2, "count") == 0) &&
-        (qlo & (TAB_NB - 1)) == 0 && (qhi & (TAB_NB - 1)) == 0) {
+        !(c->p.flags & KMER_FLAG_TABLE_SPLIT_TEST) && (qlo & (TAB_NB - 1)) == 0 && (qhi & (TAB_NB - 1)) == 0) {
         capq = cap6(qg * mu);
         rpp = (TAB_NB + qg - 1) / qg;
         gmag = ((1u << 20) + qg - 1) / qg;
@@ -443,12 +425,10 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     f.out = c->t_ent;
     f.nd = c->tnd.p;
     const uint64_t mean = (n - std::min(n, c->t_fill)) / TAB_NQ;   // (keys, not filler slots)
-    uint64_t range_keys = 3000;               // mean keys per LDS range (load ~0.37: short probing; measured best at C3)
-    if (const char *rk = exp_env("KMERHIP_TAB_RANGE")) range_keys = std::max<uint64_t>(64, strtoull(rk, nullptr, 10));
+    const uint64_t range_keys = 3000;         // mean keys per LDS range (load ~0.37: short probing; measured best at C3)
     while (f.sub_bits < 16 && (mean >> f.sub_bits) > range_keys) ++f.sub_bits;
     f.range_keys = (uint32_t)std::min<uint64_t>(range_keys, TAB_CAP);
     f.cap = (c->p.flags & KMER_FLAG_TABLE_SPLIT_TEST) ? 64 : TAB_CAP;
-    if (const char *ab = exp_env("KMERHIP_TAB_ABLATE")) f.ablate = (uint32_t)atoi(ab);   // experiments only
     f.big = c->tbig.p;
     f.big_count = c->tstats.p + 3;
     f.big_cap = c->tbig.cap;
@@ -469,23 +449,10 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     f.qhi = qhi;
     if (qlo != 0 || qhi != TAB_NQ) HIPCHK(c, hipMemsetAsync(c->tnd.p, 0, TAB_NQ * sizeof(uint32_t), s));
     const uint32_t fgrid = (uint32_t)std::max(c->n_cu, 1);
-    std::vector<uint64_t> hprof;
-#ifdef TAB_PROF
-    if (exp_env("KMERHIP_TAB_PROF")) {         // experiments (-DTAB_PROF build): per-phase clocks of the final kernel
-#else
-    if (false) {
-#endif
-        HIPCHK(c, hipMalloc((void **)&f.prof, fgrid * 64ull));
-        HIPCHK(c, hipMemsetAsync(f.prof, 0, fgrid * 64ull, s));
-        hprof.resize(fgrid * 8ull);
-    }
     // the sort kernel (two workgroups per CU) takes every unit it can; the
     // general kernel (hash path, range splits) takes the ones it leaves
-    // (crowded buckets, many copies of a key).  KMERHIP_TAB_FINAL=general: the
-    // general kernel alone (A/B experiments).
-    const char *fk = exp_env("KMERHIP_TAB_FINAL");
-    const bool sort_first = !(fk && strcmp(fk, "general") == 0) && !f.prof &&
-                            !(c->p.flags & KMER_FLAG_TABLE_SPLIT_TEST);
+    // (crowded buckets, many copies of a key).
+    const bool sort_first = !(c->p.flags & KMER_FLAG_TABLE_SPLIT_TEST);
     HIPCHK(c, hipEventRecord(c->tev[2], s));
     if (sort_first) {
         HIPCHK(c, c->tleft.ensure(2ull * TAB_NQ + 1, s));
@@ -496,21 +463,6 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     }
     HIPCHK(c, launch_tab_final(f, fgrid, s));
     HIPCHK(c, hipEventRecord(c->tev[7], s));
-    if (f.prof) {
-        HIPCHK(c, hipMemcpyAsync(hprof.data(), f.prof, fgrid * 64ull, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        (void)hipFree(f.prof);
-        double ph[6] = {0, 0, 0, 0, 0, 0};
-        uint64_t ranges = 0, buckets = 0;
-        for (uint32_t g = 0; g < fgrid; ++g) {
-            for (int i = 0; i < 6; ++i) ph[i] += i == 4 ? 0 : (double)hprof[g * 8 + i] * 0.01 / fgrid;   // us
-            ranges += hprof[g * 8 + 4] >> 32;
-            buckets += hprof[g * 8 + 4] & 0xFFFFFFFFull;
-        }
-        fprintf(stderr, "tab_final prof (us per workgroup): load+setup %.0f range-syncs %.0f insert %.0f emit %.0f "
-                        "empty %.0f | buckets %llu ranges %llu sub_bits %u\n", ph[0], ph[1], ph[2], ph[3], ph[5],
-                (unsigned long long)buckets, (unsigned long long)ranges, f.sub_bits);
-    }
     HIPCHK(c, hipMemcpyAsync(c->h_small + 8, c->tstats.p, 4 * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(c->h_small, c->d_scal, 8 * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));

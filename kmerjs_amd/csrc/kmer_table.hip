@@ -31,8 +31,6 @@
 //           atomic count) with ranges split and redone when they do not fit.
 //           Entries (remainder, count) are written back to the bucket's range;
 //           Map statistics on the fly.
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "kmer_device.hpp"
@@ -43,7 +41,6 @@ namespace {
 
 constexpr int TAB_RPL = 16;                  // segments (keys) per lane per round
 constexpr int TAB_WG1 = 1024;                // scatter workgroup (16 waves)
-constexpr int TAB_ROUND = TAB_RPL * TAB_WG1; // keys sorted in LDS per round
 constexpr uint64_t TAB_EMPTY = 1ull << 63;   // empty slot (remainders are < 2^44)
 constexpr uint64_t TAB_RMASK = (1ull << TAB_RBITS) - 1;
 
@@ -116,12 +113,6 @@ __device__ __forceinline__ uint64_t tab_brev64(uint64_t x) {
 }
 
 __device__ __forceinline__ uint64_t tab_key(const TabArgs &a, uint64_t cf, uint64_t cr) {
-#ifdef KMERHIP_EXPERIMENTS
-    if (a.narrow == 2) {                             // (A/B only, results WRONG: the cost of the mix)
-        const uint64_t c = tab_canon_n(cf, cr, a.k);
-        return (c << 54) | ((c >> 10) << TAB_NSH);
-    }
-#endif
     return a.narrow ? tab_mix_n(tab_canon_n(cf, cr, a.k)) : tab_mix(cf < cr ? cf : cr);
 }
 
@@ -287,11 +278,12 @@ __global__ __launch_bounds__(256) void tab_hist1_kernel(TabArgs a) {
     for (uint32_t i = threadIdx.x; i < TAB_NB; i += 256) a.H1[(uint64_t)i * a.nwg + blockIdx.x] = hist[i];
 }
 
-// pass 1, scatter in half-size workgroups: 512 threads, rounds of 8 K keys,
-// 80 KB of LDS -- two workgroups per CU, so that one's write-out overlaps the
-// other's window formation (one 1,024-thread workgroup per CU runs its
-// formation, LDS sort and stores strictly one after another).  Thread t keeps
-// bins 2t and 2t + 1.
+// pass 1, scatter: the same keys, LDS-sorted by partition and written as one
+// contiguous run per partition and round.  Half-size workgroups: 512 threads,
+// rounds of 8 K keys, 80 KB of LDS -- two workgroups per CU, so that one's
+// write-out overlaps the other's window formation (one 1,024-thread workgroup
+// per CU runs its formation, LDS sort and stores strictly one after another).
+// Thread t keeps bins 2t and 2t + 1.
 constexpr int TAB_WGH = 512;
 template <bool PFX>
 __global__ __launch_bounds__(TAB_WGH) void tab_scatter1h_kernel(TabArgs a) {
@@ -443,51 +435,6 @@ __global__ __launch_bounds__(256) void tab_wg_windows_kernel(const SeqLine *line
     if (threadIdx.x == 0) W[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
-// pass 1, scatter: the same keys, LDS-sorted by partition in rounds of 16 K,
-// written as one contiguous run per partition and round
-template <bool PFX>
-__global__ __launch_bounds__(TAB_WG1) void tab_scatter1_kernel(TabArgs a) {
-    __shared__ uint64_t srt[TAB_ROUND];
-    __shared__ uint64_t cur[TAB_NB];
-    __shared__ uint32_t bcnt[TAB_NB], bst[TAB_NB];
-    __shared__ uint32_t ws[16];
-    const uint32_t t = threadIdx.x;
-    cur[t] = a.base + a.H1s[(uint64_t)t * a.nwg + blockIdx.x];
-    bcnt[t] = 0;
-    __syncthreads();
-    TabCur c = tab_cursor(a, TAB_WG1 / 64);
-    while (true) {
-        uint64_t key[TAB_RPL];
-        uint32_t rank[TAB_RPL];
-        uint32_t v = 0;
-        if (c.m < c.end) v = tab_round<TAB_RPL, 0, PFX>(a, c, true, key);
-#pragma unroll
-        for (int j = 0; j < TAB_RPL; ++j)
-            rank[j] = (v & (1u << j)) ? atomicAdd(&bcnt[key[j] >> (64 - TAB_L1)], 1u) : 0u;
-        __syncthreads();
-        uint32_t total;
-        const uint32_t cnt = bcnt[t];
-        const uint32_t my_st = block_excl_1024(cnt, ws, &total);
-        bst[t] = my_st;
-        cur[t] -= my_st;                          // (write-out: B1[cur[p] + i], one LDS read per key)
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < TAB_RPL; ++j)
-            if (v & (1u << j)) srt[bst[key[j] >> (64 - TAB_L1)] + rank[j]] = key[j];
-        __syncthreads();
-#ifndef TAB_EXP_S1_NOSTORE                         // (experiment builds only)
-        for (uint32_t i = t; i < total; i += TAB_WG1) {
-            const uint64_t h = srt[i];
-            b1_store(a, cur[(uint32_t)(h >> (64 - TAB_L1))] + i, h);
-        }
-#endif
-        __syncthreads();
-        cur[t] += my_st + cnt;
-        bcnt[t] = 0;
-        if (!__syncthreads_or(c.m < c.end)) break;
-    }
-}
-
 // Long lines (contigs) are cut into pieces of <= TAB_PIECE windows, so that
 // pass 1's per-workgroup shares of lines carry similar work: table mode has no
 // order, so a piece is just a shorter line (its k-1 byte overlap with the next
@@ -569,75 +516,8 @@ __global__ __launch_bounds__(256) void tab_hist2_kernel(const uint64_t *B1, cons
     for (uint32_t b = threadIdx.x; b < TAB_NB; b += 256) H2[un.hbase + (uint64_t)b * un.nunits + un.u] = hist[b];
 }
 
-// pass 2, scatter: a unit's keys into their buckets (LDS sort per round)
-__global__ __launch_bounds__(TAB_WG1) void tab_scatter2_kernel(const uint64_t *B1, const TabUnit *units,
-                                                               const uint64_t *H2s, uint64_t *B2) {
-    __shared__ uint64_t srt[TAB_ROUND];
-    __shared__ uint64_t cur[TAB_NB];
-    __shared__ uint32_t bcnt[TAB_NB], bst[TAB_NB];
-    __shared__ uint32_t ws[16];
-    const uint32_t t = threadIdx.x;
-    const TabUnit un = units[blockIdx.x];
-    const uint64_t *src = B1 + un.start;
-#ifdef TAB_EXP_S2_COPY                            // (experiment builds only: a plain streaming copy)
-    for (uint32_t i = t; i < un.len; i += TAB_WG1) B2[un.start + i] = src[i];
-    return;
-#endif
-    cur[t] = H2s[un.hbase + (uint64_t)t * un.nunits + un.u];
-    bcnt[t] = 0;
-    __syncthreads();
-    // the next round's keys are loaded as soon as this round's sit in LDS, in
-    // flight while the round is written out
-    uint64_t key[TAB_RPL];
-#pragma unroll
-    for (int j = 0; j < TAB_RPL; ++j) {
-        const uint32_t i = j * TAB_WG1 + t;
-        key[j] = i < un.len ? src[i] : 0;
-    }
-    for (uint32_t r0 = 0; r0 < un.len; r0 += TAB_ROUND) {
-        uint32_t rank[TAB_RPL];
-#pragma unroll
-        for (int j = 0; j < TAB_RPL; ++j) {
-            const uint32_t i = r0 + j * TAB_WG1 + t;
-            rank[j] = i < un.len && key[j] != TAB_SENT
-                          ? atomicAdd(&bcnt[(uint32_t)(key[j] >> TAB_RBITS) & (TAB_NB - 1)], 1u) : 0u;
-        }
-        __syncthreads();
-        uint32_t total;
-        const uint32_t cnt = bcnt[t];
-        const uint32_t my_st = block_excl_1024(cnt, ws, &total);
-        bst[t] = my_st;
-        cur[t] -= my_st;                          // (write-out: B2[cur[b] + i], one LDS read per key)
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < TAB_RPL; ++j) {
-            const uint32_t i = r0 + j * TAB_WG1 + t;
-            if (i < un.len && key[j] != TAB_SENT) srt[bst[(uint32_t)(key[j] >> TAB_RBITS) & (TAB_NB - 1)] + rank[j]] = key[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < TAB_RPL; ++j) {
-            const uint32_t i = r0 + TAB_ROUND + j * TAB_WG1 + t;
-            key[j] = i < un.len ? src[i] : 0;
-        }
-#ifndef TAB_EXP_S2_NOSTORE                         // (experiment builds only: -DTAB_EXP_S2_NOSTORE)
-        for (uint32_t i = t; i < total; i += TAB_WG1) {
-            const uint64_t h = srt[i];
-#ifdef TAB_EXP_NT
-            __builtin_nontemporal_store(h, &B2[cur[(uint32_t)(h >> TAB_RBITS) & (TAB_NB - 1)] + i]);
-#else
-            B2[cur[(uint32_t)(h >> TAB_RBITS) & (TAB_NB - 1)] + i] = h;
-#endif
-        }
-#endif
-        __syncthreads();
-        cur[t] += my_st + cnt;
-        bcnt[t] = 0;
-        __syncthreads();
-    }
-}
-
-// pass 2, scatter with aligned write-out: rounds of 8 K keys; each bucket's
+// pass 2, scatter: a unit's keys into their buckets (LDS sort per round),
+// with aligned write-out: rounds of 10 K keys; each bucket's
 // keys of a round go out only up to the last 64-B boundary of its B2 range
 // (8 keys), the rest (<= 7 keys) is carried in the bucket owner's registers
 // into the next round's LDS sort.  A round then writes whole 64-B blocks
@@ -1033,20 +913,6 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
     const uint64_t rk = a.range_keys;
     uint64_t st_canon = 0, st_keys = 0, st_sum = 0;
     uint64_t kn[TAB_KPT];
-    // (experiments: phase clocks of wave 0, 100 MHz, in a -DTAB_PROF build only)
-#ifdef TAB_PROF
-    const bool prof = a.prof != nullptr && t == 0;
-#else
-    constexpr bool prof = false;
-#endif
-    uint64_t pt[6] = {0, 0, 0, 0, 0, 0}, tm = prof ? wall_clock64() : 0;
-    auto mark = [&](int p) {
-        if (prof) {
-            const uint64_t x = wall_clock64();
-            pt[p] += x - tm;
-            tm = x;
-        }
-    };
     // a unit's keys (lanes past its end re-read its first key and are masked
     // at use): unconditional loads, all in flight together
     // (narrow B2, b2n: 32-bit keys h >> 23 without the partition bits, which
@@ -1104,7 +970,7 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
     // start cache must hold u's start, i.e. u <= cbase + TAB_SC)
     // (groups for the sort path fill the registers; the hash path's ranges
     // split a group whose distinct keys overflow the table)
-    const uint64_t gk = !(KH_ABLATE(a) & 4) ? (uint64_t)TAB_REG_MAX : rk;
+    const uint64_t gk = TAB_REG_MAX;
     // (fixed-capacity buckets, capq: one bucket per unit, keys at B2[q capq ..
     // q capq + inlen[q]), entries out at start[q])
     // (regions of qg buckets: u is a region's first bucket; the general kernel
@@ -1163,7 +1029,6 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
         if (n == 0) {
             for (uint32_t i = t; i < g; i += TAB_FWG) a.nd[q + i] = 0;
             if (more) load_keys(qn, s0n, nn);
-            mark(5);
             q = qn;
             qe = qne;
             continue;
@@ -1187,9 +1052,6 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
         for (uint32_t i = t; i < g; i += TAB_FWG) nout[i] = 0;
 #pragma unroll
         for (int j = 0; j < TAB_KPT; ++j) kn[j] -= qbase;
-        if (prof)
-            for (int j = 0; j < TAB_KPT; ++j) asm volatile("" ::"v"(kn[j]));   // (clock after the key loads)
-        mark(0);
         // Sort path (any unit held in registers: one bucket at C3, a group of
         // up to 64 small buckets at C5).  A counting sort of the unit's keys
         // into 4,096 LDS bins by their top 12 bits, then every thread dedupes
@@ -1197,7 +1059,7 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
         // LDS atomic per key and plain LDS stores, instead of a CAS + a count
         // add per key (plus probing) and a slot scan per range.  A unit with a
         // crowded run of bins (many copies of one key) takes the hash path below.
-        if (inreg && !(KH_ABLATE(a) & 4)) {
+        if (inreg) {
             // bins: the top 12 bits of (bucket offset << 44 | remainder), so a
             // group's buckets occupy consecutive bin ranges
             const uint32_t bsh = TAB_RBITS + (g > 1 ? 32 - __clz(g - 1) : 0) - 12;
@@ -1288,7 +1150,6 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
                 __syncthreads();
                 for (uint32_t i = t; i < g; i += TAB_FWG) a.nd[q + i] = nout[i];
                 dirty = true;                    // the hash path clears the table before use
-                if (prof) pt[4] += 1;
                 q = qn;
                 qe = qne;
                 continue;
@@ -1313,14 +1174,12 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
                 ovf = 0;
             }
             __syncthreads();
-            mark(1);
-            if (prof) pt[4] += 1ull << 32;       // ranges
             if (inreg) {
                 uint32_t pend = 0;
                 const int left = (int)n - (int)t;
 #pragma unroll
                 for (int j = 0; j < TAB_KPT; ++j)
-                    if (left > j * (int)TAB_FWG && kn[j] >= rlo && kn[j] < rhi && !(KH_ABLATE(a) & 1)) pend |= 1u << j;
+                    if (left > j * (int)TAB_FWG && kn[j] >= rlo && kn[j] < rhi) pend |= 1u << j;
                 // (groups of four keys: enough CAS round trips in flight
                 // without spilling the held keys)
                 uint32_t cl = 0;
@@ -1344,7 +1203,6 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
             __syncthreads();
             if (t == 0 && occ > a.cap) ovf = 1u;     // more distinct keys than the range may hold
             __syncthreads();
-            mark(2);
             if (ovf) {
                 for (uint32_t i = t; i < TAB_SLOTS; i += TAB_FWG) {
                     tkey[i] = TAB_EMPTY;
@@ -1370,7 +1228,7 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
             // emit (and clear) the occupied slots: per wave, one LDS counter
             // bump per bucket present among the wave's entries
 #pragma unroll 1
-            for (uint32_t i = t; i < TAB_SLOTS && !(KH_ABLATE(a) & 2); i += TAB_FWG) {
+            for (uint32_t i = t; i < TAB_SLOTS; i += TAB_FWG) {
                 const uint64_t key = tkey[i];
                 const bool v = key != TAB_EMPTY;
                 uint64_t m = __ballot(v);
@@ -1416,18 +1274,14 @@ __global__ __launch_bounds__(TAB_FWG) void tab_final_kernel(TabFinal a) {
                 }
                 account(h, cnt);
             }
-            mark(3);
         }
         // (the range loop left after a barrier: every emission bump is in nout)
         for (uint32_t i = t; i < g; i += TAB_FWG) a.nd[q + i] = nout[i];
-        if (prof) pt[4] += g;                        // buckets
         q = qn;
         qe = qne;
     }
     __syncthreads();                                 // (the next item refills the start cache)
     }
-    if (prof)
-        for (int i = 0; i < 6; ++i) a.prof[blockIdx.x * 8 + i] = pt[i];
     {
         __shared__ unsigned long long red[16][3];
         tab_stats_out(a.stats, st_canon, st_keys, st_sum, TAB_FWG / 64, red);
@@ -1727,10 +1581,10 @@ __global__ __launch_bounds__(TAB_SWG, 4) void tab_sort_final_kernel(TabFinal a) 
                     const bool valid = left > j * (int)TAB_SWG;
                     const uint32_t b = pk[j] >> 14;
                     const uint32_t b0 = (bst[b >> 1] >> (16 * (b & 1u))) & 0xFFFFu;
-                    const uint32_t b1 = (KH_ABLATE(a) & 8) ? b0 : b + 1 < NB ? (bst[(b + 1) >> 1] >> (16 * ((b + 1) & 1u))) & 0xFFFFu : (uint32_t)n;
+                    const uint32_t b1 = b + 1 < NB ? (bst[(b + 1) >> 1] >> (16 * ((b + 1) & 1u))) & 0xFFFFu : (uint32_t)n;
                     const uint32_t c = valid ? b1 - b0 : 0u;
                     bb[u] = b0 | c << 14;
-                    cf[u] = valid ? ((KH_ABLATE(a) & 8) ? 0x101u : 0x100u) : 0u;   // (experiments: no bin scan)
+                    cf[u] = valid ? 0x100u : 0u;
                     cmax = max(cmax, c);
                 }
                 for (uint32_t m = 0; m < cmax; ++m) {
@@ -1793,10 +1647,9 @@ __global__ __launch_bounds__(TAB_SWG, 4) void tab_sort_final_kernel(TabFinal a) 
                         }
                     }
                     if (first) {
-                        if (!(KH_ABLATE(a) & 32))
-                            a.out[(single ? s0 : a.capq ? s0 + (bst[(ql << sbb) >> 1] & 0xFFFFu) : sc[q + ql - cbase]) + pos] =
-                                ((xj & TAB_RMASK) << 20) | cnt;
-                        if (!(KH_ABLATE(a) & 16)) account(qbase + xj, cnt);
+                        a.out[(single ? s0 : a.capq ? s0 + (bst[(ql << sbb) >> 1] & 0xFFFFu) : sc[q + ql - cbase]) + pos] =
+                            ((xj & TAB_RMASK) << 20) | cnt;
+                        account(qbase + xj, cnt);
                     }
                 }
             }
@@ -1835,22 +1688,10 @@ hipError_t launch_tab_hist1(const TabArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_tab_scatter1(const TabArgs &a, hipStream_t s) {
-    // KMERHIP_TAB_S1=full: one 1,024-thread workgroup per CU (A/B experiments)
-    static const bool half = [] {
-        const char *e = exp_env("KMERHIP_TAB_S1");
-        return !(e && strcmp(e, "full") == 0);
-    }();
-    if (half) {
-        if (a.pmask == 0)
-            hipLaunchKernelGGL(tab_scatter1h_kernel<false>, dim3(a.nwg), dim3(TAB_WGH), 0, s, a);
-        else
-            hipLaunchKernelGGL(tab_scatter1h_kernel<true>, dim3(a.nwg), dim3(TAB_WGH), 0, s, a);
-        return hipGetLastError();
-    }
     if (a.pmask == 0)
-        hipLaunchKernelGGL(tab_scatter1_kernel<false>, dim3(a.nwg), dim3(TAB_WG1), 0, s, a);
+        hipLaunchKernelGGL(tab_scatter1h_kernel<false>, dim3(a.nwg), dim3(TAB_WGH), 0, s, a);
     else
-        hipLaunchKernelGGL(tab_scatter1_kernel<true>, dim3(a.nwg), dim3(TAB_WG1), 0, s, a);
+        hipLaunchKernelGGL(tab_scatter1h_kernel<true>, dim3(a.nwg), dim3(TAB_WGH), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1882,15 +1723,7 @@ hipError_t launch_tab_hist2(const uint64_t *B1, const TabUnit *units, uint32_t n
 
 hipError_t launch_tab_scatter2(const uint64_t *B1, const TabUnit *units, uint32_t n_units, const uint64_t *H2s,
                                uint64_t *B2, hipStream_t s) {
-    // KMERHIP_TAB_S2=plain: the 16 K-round kernel without aligned write-out (A/B experiments)
-    static const bool plain = [] {
-        const char *e = exp_env("KMERHIP_TAB_S2");
-        return e && strcmp(e, "plain") == 0;
-    }();
-    if (plain)
-        hipLaunchKernelGGL(tab_scatter2_kernel, dim3(n_units), dim3(TAB_WG1), 0, s, B1, units, H2s, B2);
-    else
-        hipLaunchKernelGGL(tab_scatter2c_kernel, dim3(n_units), dim3(TAB_WG1), 0, s, B1, units, H2s, B2);
+    hipLaunchKernelGGL(tab_scatter2c_kernel, dim3(n_units), dim3(TAB_WG1), 0, s, B1, units, H2s, B2);
     return hipGetLastError();
 }
 
@@ -1977,13 +1810,8 @@ hipError_t launch_tab_digest(const uint64_t *ent, const uint64_t *start, const u
 }
 
 hipError_t launch_tab_sort_final(const TabFinal &a, uint32_t grid, hipStream_t s) {
-    // (16,384 bins for fixed regions of one wide bucket or of narrow keys;
-    // KMERHIP_TAB_BINS=8192: always 8,192, A/B experiments)
-    static const bool big_ok = [] {
-        const char *e = exp_env("KMERHIP_TAB_BINS");
-        return !(e && strcmp(e, "8192") == 0);
-    }();
-    if (a.capq && a.capq <= TAB_SORT_KEYS_BIG && (a.qg == 1 || a.b2n) && big_ok)
+    // (16,384 bins for fixed regions of one wide bucket or of narrow keys)
+    if (a.capq && a.capq <= TAB_SORT_KEYS_BIG && (a.qg == 1 || a.b2n))
         hipLaunchKernelGGL(tab_sort_final_kernel<14>, dim3(grid), dim3(TAB_SWG), 0, s, a);
     else
         hipLaunchKernelGGL(tab_sort_final_kernel<13>, dim3(grid), dim3(TAB_SWG), 0, s, a);

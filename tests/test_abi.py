@@ -56,18 +56,22 @@ def test_product_does_not_reference_oracle():
                 assert "oracle" not in src.replace("oracle/kmer_oracle.c", ""), fn
 
 
-EXPERIMENT_ENV = ("KMERHIP_TAB_ABLATE", "KMERHIP_TAB_RANGE", "KMERHIP_TAB_FINAL", "KMERHIP_NL", "KMERHIP_TAB_S1",
-                  "KMERHIP_TAB_S2", "KMERHIP_ONE_STREAM", "KMERHIP_TAB_PROF", "KMERHIP_DENSE")
-
-
 def test_shipping_library_has_no_experiment_switches():
-    """the A/B switches exist only in a -DKMERHIP_EXPERIMENTS
-    build (tools/); the default library cannot read them, so a stray variable
-    in a user's environment changes nothing."""
+    """there is one build of the library, and it reads no
+    environment variable, so a stray variable in a user's environment changes
+    nothing.  No KMERHIP_* name occurs in the binary, and no source reads the
+    environment or has a second configuration."""
     with open(os.path.join(REPO, "kmerjs_amd", "libkmerhip.so"), "rb") as f:
         blob = f.read()
-    present = [n for n in EXPERIMENT_ENV if n.encode() in blob]
-    assert not present, present
+    assert b"KMERHIP_" not in blob
+    csrc = os.path.join(REPO, "kmerjs_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, fn)
+        if not os.path.isfile(path):
+            continue
+        with open(path, encoding="utf-8") as f:
+            src = f.read()
+        assert "getenv" not in src and "KMERHIP_EXPERIMENTS" not in src, fn
 
 
 def test_header_has_no_result_corrupting_flag():
