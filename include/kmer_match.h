@@ -10,6 +10,8 @@
  *   findKmersMatchesRedis: one lrange per query k-mer,    kmer_match_open
  *     templates scored in first-hit order                 (+ kmer_match_templates)
  *     (lib/kmerFinderServer.js:171-226)
+ *   the same with a Map too large to build (2^24 keys):   kmer_match_open_table
+ *     the query stays in the counter's device table       (+ kmer_db_kmers)
  *   findWinner: templates sorted by uScore, first wins    kmer_match_winner
  *     (:741-752, sortKmerMatches :700-709)
  *   removeWinnerKmers + getMatches: the winner's k-mers   kmer_match_remove
@@ -72,6 +74,36 @@ kmer_status kmer_match_open(kmer_db *db, const char *keys, const uint64_t *offse
  * legacy default stream): the match waits for the work queued on it so far. */
 kmer_status kmer_match_open_device(kmer_db *db, const void *d_keys, uint32_t klen, const void *d_counts,
                                    uint64_t n, void *stream, kmer_match **out);
+/* The same with a table-mode count as the query (KMER_FLAG_UNORDERED /
+ * KMER_FLAG_CANONICAL, after a table finish): the Map that `ctx`'s finished
+ * table describes — the one its host result lists and its lookup answers for.
+ * The join runs from the DB's side, on the device, where the table lies:
+ *   - query k-mer i is the DB's i-th distinct k-mer in ascending string order
+ *     (A < C < G < T); n = the DB's distinct count (kmer_db_info);
+ *   - a DB k-mer is in the query iff its Map value is > 0, and that value is
+ *     its count.  The value is the lookup's: 0 unless the key starts with the
+ *     context's prefix (canonical mode: and is the smaller string of the key
+ *     and its reverse complement); a self-complementary key counts both
+ *     strands' windows (not in canonical mode); keys with a byte outside
+ *     A/C/G/T are never matched (the DB has none).
+ * The table's host result is sorted by key bytes, as the DB's distinct k-mers
+ * are, so templates, first-hit order, DB order, uScore, tScore, hits, every
+ * winner and the scores after every remove equal those of the host-array open
+ * over that host result in its own order.  Only a query index means something
+ * else: an index into the DB's distinct k-mers (template_kmers; `removed`
+ * writes `distinct` bytes); the DB decodes such indices back into k-mers.
+ * The counts are copied: after the call the context may be reset, reused or
+ * closed; its table is left unchanged.  A chunk still in flight on the
+ * context is settled first.
+ * KMER_E_STATE: a group context, a context not in table mode or without a
+ * table finish.  KMER_E_BAD_PARAM: the context is on another device than the
+ * DB.  A context whose k differs from the DB's gives a match without hits
+ * (strings of different length never compare equal), as an empty table or an
+ * empty DB does.  An exchanged table matches its own share of the classes. */
+kmer_status kmer_match_open_table(kmer_db *db, kmer_ctx *ctx, kmer_match **out);
+/* The DB's distinct k-mers [first, first + n) in ascending order, n * k bytes
+ * back to back.  KMER_E_BAD_PARAM for a range past `distinct`. */
+kmer_status kmer_db_kmers(const kmer_db *db, uint64_t first, uint64_t n, char *keys);
 /* Current hits (sum of uScore) and templates with uScore > 0. */
 kmer_status kmer_match_info(kmer_match *m, uint64_t *hits, uint32_t *n_templates);
 

@@ -40,7 +40,8 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_table_lookup", "kmer_table_lookup_device",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
-MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_close", "kmer_match_open", "kmer_match_open_device",
+MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_kmers", "kmer_db_close", "kmer_match_open",
+                 "kmer_match_open_device", "kmer_match_open_table",
                  "kmer_match_info", "kmer_match_templates", "kmer_match_template_kmers", "kmer_match_winner", "kmer_match_remove",
                  "kmer_match_removed", "kmer_match_close", "kmer_match_last_error"]
 EXPORTS = EXPORTS + MATCH_EXPORTS
@@ -140,6 +141,8 @@ def _load():
         "kmer_db_close": (ctypes.c_int, [vp]),
         "kmer_match_open": (ctypes.c_int, [vp, vp, pu64, pu64, u64, ctypes.POINTER(vp)]),
         "kmer_match_open_device": (ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, u64, vp, ctypes.POINTER(vp)]),
+        "kmer_match_open_table": (ctypes.c_int, [vp, vp, ctypes.POINTER(vp)]),
+        "kmer_db_kmers": (ctypes.c_int, [vp, u64, u64, vp]),
         "kmer_match_info": (ctypes.c_int, [vp, pu64, ctypes.POINTER(ctypes.c_uint32)]),
         "kmer_match_templates": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                                 pu64, pu64, ctypes.POINTER(ctypes.c_uint32)]),

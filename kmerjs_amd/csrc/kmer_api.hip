@@ -806,6 +806,32 @@ static kmer_status lookup_state(kmer_ctx *c) {
     return KMER_OK;
 }
 
+// The finished table (not empty) as its readers see it: the one place that
+// names the context's table buffers (the lookup below; the matcher's probe
+// through table_view)
+static kmer_status fill_view(kmer_ctx *c, TabView *v) {
+    if (!c->t_ent || !c->tstart.p || !c->tnd.p || !c->tbig.p) return fail(c, KMER_E_STATE, "no table finish yet");
+    HIPCHK(c, c->tlk_bad.ensure(1, c->stream));
+    memset(v, 0, sizeof(*v));
+    v->ent = c->t_ent;
+    v->start = c->tstart.p;
+    v->nd = c->tnd.p;
+    v->cap = c->t_keys;
+    v->big = c->tbig.p;
+    v->n_big = std::min<uint64_t>(c->t_nbig, c->tbig.cap);
+    v->k = c->p.k;
+    for (size_t i = 0; i < c->prefix.size(); ++i) {
+        const uint8_t ch = (uint8_t)c->prefix[i];
+        v->plo |= ((((uint32_t)ch >> 1) ^ ((uint32_t)ch >> 2)) & 1u) << i;
+        v->phi |= (((uint32_t)ch >> 2) & 1u) << i;
+    }
+    v->pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
+    v->canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
+    v->err = c->d_err;
+    v->badq = c->tlk_bad.p;
+    return KMER_OK;
+}
+
 // The lookup of n device-resident keys, queued on the context's stream and
 // waited for; a refused bucket extent (ERR_TAB_LOOKUP) is reported here.
 static kmer_status lookup_run(kmer_ctx *c, const uint8_t *d_keys, uint64_t n, uint64_t *d_counts) {
@@ -815,29 +841,13 @@ static kmer_status lookup_run(kmer_ctx *c, const uint8_t *d_keys, uint64_t n, ui
         HIPCHK(c, hipStreamSynchronize(s));
         return KMER_OK;
     }
-    if (!c->t_ent || !c->tstart.p || !c->tnd.p || !c->tbig.p) return fail(c, KMER_E_STATE, "no table finish yet");
-    HIPCHK(c, c->tlk_bad.ensure(1, s));
     TabLookup a;
     memset(&a, 0, sizeof(a));
+    const kmer_status vs = fill_view(c, &a);
+    if (vs) return vs;
     a.keys = d_keys;
     a.n = n;
     a.counts = d_counts;
-    a.ent = c->t_ent;
-    a.start = c->tstart.p;
-    a.nd = c->tnd.p;
-    a.cap = c->t_keys;
-    a.big = c->tbig.p;
-    a.n_big = std::min<uint64_t>(c->t_nbig, c->tbig.cap);
-    a.k = c->p.k;
-    for (size_t i = 0; i < c->prefix.size(); ++i) {
-        const uint8_t ch = (uint8_t)c->prefix[i];
-        a.plo |= ((((uint32_t)ch >> 1) ^ ((uint32_t)ch >> 2)) & 1u) << i;
-        a.phi |= (((uint32_t)ch >> 2) & 1u) << i;
-    }
-    a.pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
-    a.canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
-    a.err = c->d_err;
-    a.badq = c->tlk_bad.p;
     HIPCHK(c, launch_tab_lookup(a, (uint32_t)std::max(c->n_cu, 1), s));
     uint32_t e = 0, q = 0;
     HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
@@ -1084,3 +1094,19 @@ kmer_status kmer_result_write(const kmer_result *r, const char *path, uint32_t f
 void kmer_result_free(kmer_result *r) { delete r; }
 
 }  // extern "C"
+
+// kmer_match_open_table (kmer_match.hip): see kmer_internal.hpp
+static kmer_status table_view_impl(kmer_ctx *c, TabView *v, TabOwner *o) {
+    SETTLE(c);                                       // (a group context: KMER_E_STATE)
+    const kmer_status st = lookup_state(c);
+    if (st) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, KMER_E_DEVICE, "hipSetDevice failed");
+    o->stream = c->stream;
+    o->device = c->device;
+    o->k = c->p.k;
+    o->n_cu = (uint32_t)std::max(c->n_cu, 1);
+    o->empty = c->t_keys == 0;
+    return o->empty ? KMER_OK : fill_view(c, v);
+}
+
+int kmerhip::table_view(kmer_ctx *c, TabView *v, TabOwner *o) { return (int)table_view_impl(c, v, o); }

@@ -1,6 +1,6 @@
 // kmer_device.hpp — device helpers shared by the kernel translation units
 // (kmer_kernels.hip, kmer_table.hip, kmer_dense.hip, kmer_fasta.hip,
-// kmer_lookup.hip): one
+// kmer_lookup.hip, kmer_probe.hip): one
 // definition of each primitive that more than one kernel uses.  The
 // host/device contract (structs, constants, launch_* declarations) is
 // kmer_internal.hpp.
@@ -24,6 +24,10 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
 // lane i's value of v (i wave-uniform)
 __device__ __forceinline__ uint32_t readlane32(uint32_t v, uint32_t i) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
+}
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t i) {
+    return ((uint64_t)readlane32((uint32_t)(v >> 32), i) << 32) | readlane32((uint32_t)v, i);
 }
 
 // Append one record to the list (its key bytes are gathered later); a full

@@ -585,6 +585,26 @@ __host__ __device__ inline bool tab_str_le(uint64_t x, uint64_t y, uint32_t k) {
     const uint32_t j = (uint32_t)__builtin_ctz(d);
     return (((xh >> j) & 1u) * 2 + ((xl >> j) & 1u)) < (((yh >> j) & 1u) * 2 + ((yl >> j) & 1u));
 }
+// Key arithmetic of the matcher's probe (kmer_probe.hip): from a 2-bit code
+// (base j at bits 2 (k - 1 - j) + 1 .. 2 (k - 1 - j), A C G T = 0 1 2 3: the
+// matcher's pack_key) to the planar codes of the k-mer and of its reverse
+// complement
+__host__ __device__ inline uint32_t tab_even_bits(uint64_t x) {   // bits 0, 2, 4 .. 62 of x, packed
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
+    return (uint32_t)x;
+}
+__host__ __device__ inline void tab_code2_planar(uint64_t code2, uint32_t k, uint64_t *cf, uint64_t *cr) {
+    // (packed bit m belongs to base k - 1 - m: reversed into base order)
+    const uint32_t lo = __builtin_bitreverse32(tab_even_bits(code2)) >> (32 - k);
+    const uint32_t hi = __builtin_bitreverse32(tab_even_bits(code2 >> 1)) >> (32 - k);
+    *cf = ((uint64_t)hi << k) | lo;
+    *cr = tab_rc_code(*cf, k);
+}
 // the hash the table digest weighs: tab_mix(min(code(w), code(rc w))) for every k
 __host__ __device__ inline uint64_t tab_digest_key(uint64_t h, uint32_t k, bool narrow) {
     if (!narrow) return h;
@@ -726,12 +746,9 @@ constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a
 hipError_t launch_tab_digest(const uint64_t *ent, const uint64_t *start, const uint32_t *nd, uint32_t k,
                             uint32_t narrow, unsigned long long *out,
                              hipStream_t s);
-// Batched lookup against a finished table (kmer_lookup.hip): counts[i] = the
-// Map value of the k bytes at keys + i k (0: absent, filtered, or not A/C/G/T)
-struct TabLookup {
-    const uint8_t *keys;
-    uint64_t n;
-    uint64_t *counts;
+// A finished table as its readers see it (kmer_lookup.hip, kmer_probe.hip);
+// filled in one place, table_view (kmer_api.hip)
+struct TabView {
     const uint64_t *ent;           // the table: entries, TAB_NQ + 1 bucket starts, entries per bucket
     const uint64_t *start;
     const uint32_t *nd;
@@ -743,7 +760,32 @@ struct TabLookup {
     unsigned int *err;             // ERR_TAB_LOOKUP ...
     uint32_t *badq;                // ... and a bucket it was raised for
 };
+// Batched lookup against a finished table (kmer_lookup.hip): counts[i] = the
+// Map value of the k bytes at keys + i k (0: absent, filtered, or not A/C/G/T)
+struct TabLookup : TabView {
+    const uint8_t *keys;
+    uint64_t n;
+    uint64_t *counts;
+};
 hipError_t launch_tab_lookup(const TabLookup &a, uint32_t n_cu, hipStream_t s);
+// The matcher's probe of a finished table (kmer_probe.hip): the m distinct
+// k-mers of a template DB, U[i] their 2-bit codes (first base most
+// significant, ascending), O the CSR offsets of their template lists.  DB
+// k-mer i is in the query iff its Map value is > 0: qidx[i] = i or 0xFFFFFFFF,
+// hc[i] = its list length or 0, present[i] = 1 or 0, cnt[i] = the value.
+struct TabProbe : TabView {
+    const uint64_t *U, *O;
+    uint64_t m;
+    uint32_t *bkt, *bkt2, *idx, *idx2;   // scratch, m each: the probes' buckets and DB indices, sorted by bucket
+    void *tmp;                           // scratch of the sort (tab_probe_temp_bytes)
+    size_t tmp_bytes;
+    uint32_t *qidx;
+    uint64_t *hc;
+    uint32_t *present;
+    uint64_t *cnt;
+};
+hipError_t tab_probe_temp_bytes(uint64_t m, size_t *bytes);
+hipError_t launch_tab_probe(const TabProbe &a, uint32_t n_cu, hipStream_t s);
 // multi-GPU table exchange: copy n segments {src offset, dst offset, length}
 // of u64 keys (one workgroup per segment, grid-strided)
 struct TabSeg {
@@ -790,5 +832,24 @@ hipError_t launch_gen_reduce(const uint32_t *start, uint64_t ng, const uint32_t 
 hipError_t launch_permute_rows(const uint8_t *keys, const uint64_t *cnt, const uint64_t *first, const uint32_t *idx,
                                uint64_t n, uint32_t k, uint8_t *okeys, uint64_t *ocnt, uint64_t *ofirst,
                                hipStream_t s);
+
+
+}  // namespace kmerhip
+
+struct kmer_ctx;
+
+namespace kmerhip {
+
+// The finished table of a single-device table-mode context for the matcher
+// (kmer_api.hip; kmer_match_open_table): the context settled and its state
+// checked as for a lookup, the view filled.  Returns a kmer_status; on a
+// failure the message is the context's last error.
+struct TabOwner {
+    hipStream_t stream;            // the context's stream (the table's writers are queued on it)
+    int device;
+    uint32_t k, n_cu;
+    bool empty;                    // a finish with no keys: the view is not filled
+};
+int table_view(kmer_ctx *c, TabView *v, TabOwner *o);
 
 }  // namespace kmerhip

@@ -26,10 +26,6 @@ constexpr uint32_t LK_LANE_MAX = 16;     // bucket entries up to which the query
 constexpr uint32_t LK_UNROLL = 8;        // wave loads (64 entries, 512 B each) in flight per round of a wave scan
 constexpr uint32_t LK_WG_PER_CU = 7;     // workgroups of 4 waves per CU (7 waves per SIMD: the kernel's occupancy)
 
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t i) {
-    return ((uint64_t)readlane32((uint32_t)(v >> 32), i) << 32) | readlane32((uint32_t)v, i);
-}
-
 __global__ __launch_bounds__(256) void tab_lookup_kernel(const TabLookup a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;

@@ -15,6 +15,10 @@
 //               uScore = segment length, tScore = sum of counts (one wave per
 //               template), first hit = the segment's first query.  Templates
 //               ranked by (first query, template) = the Redis Map's insertion order.
+//               A table-mode count as the query (kmer_match_open_table): the
+//               join runs from the DB's side -- every U[i] is probed in the
+//               count's device table (kmer_probe.hip) and query index i IS DB
+//               k-mer i; everything from the hit counts' scan on is shared.
 //   winner:     one workgroup: max of uScore << 32 | ~rank.
 //   remove:     the winner's segment: each query k-mer still present is
 //               removed (atomic exchange) and its templates' scores drop.
@@ -33,6 +37,7 @@
 #include <vector>
 
 #include "../../include/kmer_match.h"
+#include "kmer_internal.hpp"
 
 namespace {
 
@@ -357,6 +362,14 @@ __global__ void removed_kernel(const uint32_t *qidx, const uint32_t *present, ui
         flags[i] = qidx[i] != NONE && present[i] == 0u ? 1 : 0;
 }
 
+// U[first + i] -> its k bytes
+__global__ void db_decode_kernel(const uint64_t *U, uint64_t first, uint64_t n, uint32_t k, uint8_t *keys) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t c = U[first + i];
+        for (uint32_t j = 0; j < k; ++j) keys[i * k + j] = (uint8_t)"ACGT"[(c >> (2 * (k - 1 - j))) & 3u];
+    }
+}
+
 uint32_t grid_for(uint64_t n, uint32_t block = 256, uint32_t cap = 65536) {
     const uint64_t g = (n + block - 1) / block;
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
@@ -393,6 +406,7 @@ struct kmer_db {
     DArr<uint8_t> qkeys;
     DArr<uint64_t> qoffs, hc, fkey, fkey2;
     DArr<uint32_t> pt, pt2, pq2, nhd;
+    DArr<uint32_t> pb_bkt, pb_bkt2, pb_idx, pb_idx2;   // table probe: (bucket, DB index) pairs, sorted
     Temp tmp;
     MatchBufs spare;                           // buffers of the last closed match
     bool has_spare = false;
@@ -431,6 +445,7 @@ void free_db(kmer_db *db) {
     if (db->dir) (void)hipFree(db->dir);
     db->qkeys.release(), db->qoffs.release(), db->hc.release(), db->fkey.release(), db->fkey2.release();
     db->pt.release(), db->pt2.release(), db->pq2.release(), db->nhd.release();
+    db->pb_bkt.release(), db->pb_bkt2.release(), db->pb_idx.release(), db->pb_idx2.release();
     if (db->has_spare) db->spare.release();
     if (db->s) (void)hipStreamDestroy(db->s);
     delete db;
@@ -518,12 +533,11 @@ kmer_status build_db(kmer_db *db, const char *keys, uint64_t n, const uint64_t *
     return KMER_OK;
 }
 
-kmer_status match_build(kmer_match *m, const uint8_t *dkeys, const uint64_t *doffs, uint32_t klen) {
+// The arrays of a match build (every open): per query index and per template.
+kmer_status match_alloc(kmer_match *m) {
     kmer_db *db = m->db;
-    hipStream_t s = db->s;
     const uint64_t n = m->n;
     const uint32_t nt = db->nt;
-    Temp &tmp = db->tmp;
     MatchBufs &b = m->b;
     MCHK(b.qidx.ensure(n));
     MCHK(b.present.ensure(n));
@@ -545,12 +559,21 @@ kmer_status match_build(kmer_match *m, const uint8_t *dkeys, const uint64_t *dof
     m->qidx = b.qidx.p, m->present = b.present.p, m->H = b.H.p, m->seg = b.seg.p, m->u0 = b.u0.p;
     m->cu = b.cu.p, m->t0 = b.t0.p, m->ct = b.ct.p, m->order = b.order.p, m->rank = b.rank.p;
     m->scal = b.scal.p, m->dw = b.dw.p, m->hw = b.hw;
+    return KMER_OK;
+}
+
+// Round 1 from the join's answers on (every open): qidx / present / cnt per
+// query index and the hit counts db->hc, queued on the DB's stream -> their
+// exclusive scan, the hits by template, the scores, the first-hit order.
+kmer_status match_finish(kmer_match *m) {
+    kmer_db *db = m->db;
+    hipStream_t s = db->s;
+    const uint64_t n = m->n;
+    const uint32_t nt = db->nt;
+    Temp &tmp = db->tmp;
+    MatchBufs &b = m->b;
     uint32_t *nhd = db->nhd.p;
     uint64_t *fkey = db->fkey.p, *fkey2 = db->fkey2.p, *hc = db->hc.p;
-    // hit counts per query key -> their exclusive scan
-    hipLaunchKernelGGL(q_lookup_kernel, dim3(grid_for(n)), dim3(256), 0, s, dkeys, doffs, klen, n, db->k, db->U,
-                       db->m, db->O, db->dir, db->dlo, db->dhi, db->dsh, m->qidx, hc, m->present);
-    MCHK(hipGetLastError());
     if (n) MROC(tmp, rocprim::exclusive_scan(t, b, hc, m->H, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s));
     uint64_t tail[2] = {0, 0};
     if (n) MCHK(hipMemcpyAsync(&tail[0], m->H + n - 1, 8, hipMemcpyDeviceToHost, s));
@@ -590,6 +613,57 @@ kmer_status match_build(kmer_match *m, const uint8_t *dkeys, const uint64_t *dof
     MCHK(hipGetLastError());
     MCHK(hipStreamSynchronize(s));
     return KMER_OK;
+}
+
+// the query's keys joined against U by binary search (host and device opens)
+kmer_status match_build(kmer_match *m, const uint8_t *dkeys, const uint64_t *doffs, uint32_t klen) {
+    kmer_db *db = m->db;
+    const kmer_status st = match_alloc(m);
+    if (st != KMER_OK) return st;
+    // hit counts per query key
+    hipLaunchKernelGGL(q_lookup_kernel, dim3(grid_for(m->n)), dim3(256), 0, db->s, dkeys, doffs, klen, m->n, db->k,
+                       db->U, db->m, db->O, db->dir, db->dlo, db->dhi, db->dsh, m->qidx, db->hc.p, m->present);
+    MCHK(hipGetLastError());
+    return match_finish(m);
+}
+
+// the query is a finished table: every DB k-mer probed in it (kmer_probe.hip)
+kmer_status match_build_table(kmer_match *m, kmerhip::TabProbe &a, const kmerhip::TabOwner &o) {
+    kmer_db *db = m->db;
+    hipStream_t s = db->s;
+    const uint64_t n = m->n;
+    kmer_status st = match_alloc(m);
+    if (st != KMER_OK) return st;
+    if (o.empty || o.k != db->k || n == 0) {         // no key of the DB is in the Map: no table memory touched
+        if (n) MCHK(hipMemsetAsync(m->qidx, 0xFF, n * 4, s));
+        if (n) MCHK(hipMemsetAsync(m->present, 0, n * 4, s));
+        if (n) MCHK(hipMemsetAsync(db->hc.p, 0, n * 8, s));
+        if (n) MCHK(hipMemsetAsync(m->cnt, 0, n * 8, s));
+        return match_finish(m);
+    }
+    size_t bytes = 0;
+    MCHK(kmerhip::tab_probe_temp_bytes(n, &bytes));
+    MCHK(db->tmp.ensure(bytes + 16));
+    MCHK(db->pb_bkt.ensure(n));
+    MCHK(db->pb_bkt2.ensure(n));
+    MCHK(db->pb_idx.ensure(n));
+    MCHK(db->pb_idx2.ensure(n));
+    a.U = db->U, a.O = db->O, a.m = n;
+    a.bkt = db->pb_bkt.p, a.bkt2 = db->pb_bkt2.p, a.idx = db->pb_idx.p, a.idx2 = db->pb_idx2.p;
+    a.tmp = db->tmp.p, a.tmp_bytes = bytes;
+    a.qidx = m->qidx, a.hc = db->hc.p, a.present = m->present, a.cnt = m->cnt;
+    MCHK(kmerhip::launch_tab_probe(a, o.n_cu, s));
+    uint32_t e = 0, q = 0;                           // a refused bucket extent, as in the lookup
+    MCHK(hipMemcpyAsync(&e, a.err, 4, hipMemcpyDeviceToHost, s));
+    MCHK(hipMemcpyAsync(&q, a.badq, 4, hipMemcpyDeviceToHost, s));
+    MCHK(hipStreamSynchronize(s));
+    if (e & kmerhip::ERR_TAB_LOOKUP) {
+        MCHK(hipMemsetD32Async((hipDeviceptr_t)a.err, (int)(e & ~kmerhip::ERR_TAB_LOOKUP), 1, s));
+        MCHK(hipStreamSynchronize(s));
+        return set_err(KMER_E_DEVICE,
+                       "kmer_match_open_table: the extent of bucket " + std::to_string(q) + " lies past the table");
+    }
+    return match_finish(m);
 }
 
 kmer_status match_open_common(kmer_db *db, uint64_t n, kmer_match **out, kmer_match **mm) {
@@ -727,6 +801,57 @@ kmer_status kmer_match_open_device(kmer_db *db, const void *d_keys, uint32_t kle
         return st;
     }
     *out = m;
+    return KMER_OK;
+}
+
+kmer_status kmer_match_open_table(kmer_db *db, kmer_ctx *ctx, kmer_match **out) {
+    if (!db || !ctx || !out) return set_err(KMER_E_BAD_PARAM, "kmer_match_open_table: NULL argument");
+    *out = nullptr;
+    kmerhip::TabProbe a;
+    memset(&a, 0, sizeof(a));
+    kmerhip::TabOwner o;
+    memset(&o, 0, sizeof(o));
+    kmer_status st = (kmer_status)kmerhip::table_view(ctx, &a, &o);   // (settles an in-flight chunk)
+    if (st != KMER_OK) return set_err(st, std::string("kmer_match_open_table: ") + kmer_last_error(ctx));
+    if (o.device != db->device)
+        return set_err(KMER_E_BAD_PARAM, "kmer_match_open_table: the context and the DB are on different devices");
+    kmer_match *m = nullptr;
+    st = match_open_common(db, db->m, out, &m);
+    if (st != KMER_OK) return st;
+    // the table's writers are queued on the context's stream
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ev, o.stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(db->s, ev, 0);
+    if (e == hipSuccess) e = m->b.cnt.ensure(m->n);
+    m->cnt = m->b.cnt.p;
+    st = e == hipSuccess ? match_build_table(m, a, o)
+                         : set_err(KMER_E_DEVICE, std::string("HIP error: ") + hipGetErrorString(e));
+    (void)hipStreamSynchronize(db->s);               // the table is not read after the call
+    if (ev) (void)hipEventDestroy(ev);
+    if (st != KMER_OK) {
+        m->release();
+        --m->db->live;
+        delete m;
+        return st;
+    }
+    *out = m;
+    return KMER_OK;
+}
+
+kmer_status kmer_db_kmers(const kmer_db *db, uint64_t first, uint64_t n, char *keys) {
+    if (!db || first > db->m || n > db->m - first || (n && !keys))
+        return set_err(KMER_E_BAD_PARAM, "kmer_db_kmers: NULL argument or a range past the DB's distinct k-mers");
+    if (n == 0) return KMER_OK;
+    MCHK(hipSetDevice(db->device));
+    uint8_t *d = nullptr;
+    MCHK(dalloc(&d, n * db->k));
+    hipLaunchKernelGGL(db_decode_kernel, dim3(grid_for(n)), dim3(256), 0, db->s, db->U, first, n, db->k, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(keys, d, n * db->k, hipMemcpyDeviceToHost, db->s);
+    if (e == hipSuccess) e = hipStreamSynchronize(db->s);
+    (void)hipFree(d);
+    MCHK(e);
     return KMER_OK;
 }
 

@@ -209,6 +209,16 @@ class TemplateDB:
                "kmer_db_info")
         return {"k": k.value, "templates": nt.value, "distinct": d.value, "entries": e.value}
 
+    def kmers(self, first=0, n=None):
+        """The DB's distinct k-mers [first, first + n) in ascending order, as
+        bytes (kmer_db_kmers): what a query index of a table match stands for."""
+        if n is None:
+            n = self.info()["distinct"] - first
+        buf = ctypes.create_string_buffer(max(n * self.k, 1))
+        _check(LIB.kmer_db_kmers(self.handle, first, n, buf), "kmer_db_kmers")
+        raw = buf.raw
+        return [raw[i * self.k:(i + 1) * self.k] for i in range(n)]
+
     def close(self):
         """Matches of the DB that are still open keep its device data until
         they close (kmer_db_close defers the free to the last one)."""
@@ -227,12 +237,18 @@ def default_summary(templates):
 
 
 class Match:
-    """One query joined against a TemplateDB (kmer_match_open*)."""
+    """One query joined against a TemplateDB (kmer_match_open*).  table: a
+    Counter in table mode after its finish -- the query is the Map its table
+    describes and a query index is an index into the DB's distinct k-mers
+    (TemplateDB.kmers)."""
 
-    def __init__(self, db, keys=None, counts=None, device_result=None, stream=0):
+    def __init__(self, db, keys=None, counts=None, device_result=None, stream=0, table=None):
         self.db = db
         h = ctypes.c_void_p()
-        if device_result is not None:
+        if table is not None:
+            _check(LIB.kmer_match_open_table(db.handle, table.h, ctypes.byref(h)), "kmer_match_open_table")
+            self.n = db.info()["distinct"]
+        elif device_result is not None:
             d_keys, klen, d_counts, n = device_result
             _check(LIB.kmer_match_open_device(db.handle, d_keys, klen, d_counts, n, stream, ctypes.byref(h)),
                    "kmer_match_open_device")
@@ -326,6 +342,38 @@ class KmerFinder:
         finally:
             if own:
                 match.close()
+
+    def find_matches_table(self, counter, query_size=None, with_removed=False):
+        """findMatches with a table-mode count as the query (a Counter opened
+        with FLAG_UNORDERED / FLAG_CANONICAL, after its finish): the join runs
+        on the device against the counter's table.  query_size defaults to the
+        table's distinct Map keys (the kmerMapSize of the Map the table stands
+        for).  Returns the summaries; with_removed (method 'winner'): (summaries,
+        the k-mers the winners took out of the query, as bytes, ascending)."""
+        if query_size is None:
+            query_size = counter.table_stats()[1]
+        m = Match(self.db, table=counter)
+        try:
+            out = self.find_matches(None, query_size, match=m)
+            if not with_removed:
+                return out
+            idx = np.nonzero(m.removed())[0] if self.method == "winner" else []
+            return out, self._kmers_at(idx)
+        finally:
+            m.close()
+
+    def _kmers_at(self, idx):
+        """DB k-mers at ascending indices, decoded in runs of neighbours."""
+        out, i = [], 0
+        while i < len(idx):
+            j = i
+            while j + 1 < len(idx) and idx[j + 1] - idx[i] < 4096:
+                j += 1
+            lo = int(idx[i])
+            run = self.db.kmers(lo, int(idx[j]) - lo + 1)
+            out += [run[int(x) - lo] for x in idx[i:j + 1]]
+            i = j + 1
+        return out
 
     def _standard(self, m, query_size):
         tl = m.templates(_native.ORDER_DB)
