@@ -285,9 +285,57 @@ kmer_status kmer_table_stats(kmer_ctx *ctx, uint64_t *canonical, uint64_t *keys,
  * pointers with n > 0; n == 0 is KMER_OK and touches nothing. */
 kmer_status kmer_table_lookup(kmer_ctx *ctx, const char *keys, uint64_t n, uint64_t *counts);
 kmer_status kmer_table_lookup_device(kmer_ctx *ctx, const void *d_keys, uint64_t n, void *d_counts, void *stream);
+/* The table read by value (after a table finish, until the next reset; the
+ * calls may be repeated and interleaved with stats, digest, lookup and match,
+ * and leave the table unchanged).  "The Map" is the Map this context's host
+ * result describes, the one kmer_table_lookup answers for.  A table entry is a
+ * class {x, rc x} with count C.  Table mode: key x with value C if x starts
+ * with the prefix, key rc x likewise; when x == rc x, one key with value 2 C.
+ * Canonical mode: one key, the smaller string of the class, value C, if it
+ * starts with the prefix.  Record keys (a byte outside A/C/G/T) live on the
+ * host and are counted by the host-returning calls only, as kmer_table_stats
+ * counts them.
+ *
+ * kmer_table_spectrum: the abundance spectrum (jellyfish histo).  hist = a
+ * host array of nbins uint64, 2 <= nbins <= KMER_SPECTRUM_MAX_BINS
+ * (KMER_E_BAD_PARAM otherwise); every Map key of value v adds 1 to
+ * hist[min(v, nbins - 1)], hist[0] = 0, and *top_sum (may be NULL) = the sum
+ * of the values of the keys in the last bin.  With (canonical, keys, total) of
+ * kmer_table_stats: sum hist = keys, and sum of v hist[v] over v < nbins - 1,
+ * plus top_sum, = total.  A group adds its children's histograms; the
+ * histograms of the ranks of an exchanged table add up.  The kernel keeps
+ * values up to KMER_SPECTRUM_REG_MAX in registers and values below
+ * KMER_SPECTRUM_LDS_BINS in LDS; the rest are global atomics.
+ *
+ * kmer_table_extract_device: the A/C/G/T Map keys with lo <= value <= hi
+ * (hi == 0: no upper bound; lo == 0 is 1; hi != 0 && hi < lo: n = 0), sorted
+ * ascending by key bytes: *d_keys = n * k key bytes back to back, *d_counts =
+ * n uint64 values, library-owned device memory that is complete when the call
+ * returns and valid until the next extract, reset or close on the context
+ * (kmer_match_open_device takes them as they are).  Single-device contexts
+ * only (KMER_E_STATE on a group); an exchanged table extracts its own share.
+ * The buffers are sized from a counting pass; KMER_E_OOM leaves the context
+ * usable.
+ *
+ * kmer_table_extract: the rows of the context's host result whose value is in
+ * range, in the same order (by key bytes, record keys included), computed
+ * through the device extract: only the qualifying keys are copied to the
+ * host.  On a group the children's extracts are merged by key.
+ *
+ * KMER_E_STATE unless a table finish holds results; KMER_E_BAD_PARAM for NULL
+ * out-pointers; KMER_E_DEVICE, naming the bucket, if a bucket's extent lies
+ * past the table (it is not read). */
+#define KMER_SPECTRUM_REG_MAX 4u
+#define KMER_SPECTRUM_LDS_BINS 4096u
+#define KMER_SPECTRUM_MAX_BINS (1u << 21)
+kmer_status kmer_table_spectrum(kmer_ctx *ctx, uint32_t nbins, uint64_t *hist, uint64_t *top_sum);
+kmer_status kmer_table_extract_device(kmer_ctx *ctx, uint64_t lo, uint64_t hi, const void **d_keys,
+                                      const void **d_counts, uint64_t *n);
+kmer_status kmer_table_extract(kmer_ctx *ctx, uint64_t lo, uint64_t hi, kmer_result **out);
 /* The table itself, in device memory (to read counts, use kmer_table_lookup,
  * which owns the two key encodings below; this is the raw layout for a
- * consumer that walks the whole table).  2^20 buckets; bucket q holds
+ * consumer that walks the whole table; the library's own are
+ * kmer_table_spectrum and kmer_table_extract).  2^20 buckets; bucket q holds
  * bucket_len[q] (uint32) entries at entries[bucket_start[q] ..] (uint64 each:
  * remainder << 20 | count, count == 0xFFFFF meaning "see the big list").
  * h = q << 44 | remainder = c * 0x9E3779B97F4A7C15 (mod 2^64), a bijection of the canonical

@@ -24,6 +24,11 @@ FLAG_FASTA = 1 << 16      # FASTA records (an extension; kmer_api.h)
 FLAG_TABLE_FIXED_TEST = 1 << 17   # debug: table pass 1 always with fixed runs
 FLAG_GEN_COLLIDE_TEST = 1 << 18   # debug: general-path merge takes the collision retry
 TAB_PARTS = 1024    # table mode: pass-1 partitions (ownership unit across ranks)
+# kmer_table_spectrum (include/kmer_api.h, KMER_SPECTRUM_*): values up to REG_MAX are kept in
+# registers, values below LDS_BINS in LDS; nbins is at most MAX_BINS
+SPECTRUM_REG_MAX = 4
+SPECTRUM_LDS_BINS = 4096
+SPECTRUM_MAX_BINS = 1 << 21
 WRITE_JSON = 0      # JSON.stringify(mapToJSON(map)), lib/kmers.js:46-54
 WRITE_LEGACY = 1    # "{\nkey: count,...}\n", lib/index.js:381-388
 
@@ -38,6 +43,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_last_timing", "kmer_phase_times", "kmer_table_stats", "kmer_table_digest", "kmer_table_routes", "kmer_table_device",
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
            "kmer_table_lookup", "kmer_table_lookup_device",
+           "kmer_table_spectrum", "kmer_table_extract_device", "kmer_table_extract",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
 MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_kmers", "kmer_db_close", "kmer_match_open",
@@ -131,6 +137,9 @@ def _load():
         "kmer_table_finish_exchanged": (ctypes.c_int, [vp, vp, u64, pu64, ctypes.c_uint32, ctypes.c_uint32, vp]),
         "kmer_table_lookup": (ctypes.c_int, [vp, ctypes.c_char_p, u64, pu64]),
         "kmer_table_lookup_device": (ctypes.c_int, [vp, vp, u64, vp, vp]),
+        "kmer_table_spectrum": (ctypes.c_int, [vp, ctypes.c_uint32, pu64, pu64]),
+        "kmer_table_extract_device": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp), ctypes.POINTER(vp), pu64]),
+        "kmer_table_extract": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp)]),
         "kmer_status_string": (ctypes.c_char_p, [ctypes.c_int]),
         "kmer_last_error": (ctypes.c_char_p, [vp]),
         "kmer_version": (ctypes.c_char_p, []),
@@ -430,6 +439,35 @@ class Counter:
         ordered after the work queued on `stream`, complete on return."""
         self._check(LIB.kmer_table_lookup_device(self.h, ctypes.c_void_p(d_keys), n, ctypes.c_void_p(d_counts),
                                                  ctypes.c_void_p(stream)), "table_lookup_device")
+
+    def table_spectrum(self, nbins=256):
+        """Table mode, after a finish: the abundance spectrum of the Map --
+        (hist, top_sum), hist[v] (numpy uint64, nbins bins) = the distinct Map
+        keys of value v, the last bin holding every value >= nbins - 1, and
+        top_sum the sum of that bin's values."""
+        import numpy as np
+        hist = np.zeros(max(int(nbins), 1), dtype=np.uint64)
+        top = ctypes.c_uint64()
+        self._check(LIB.kmer_table_spectrum(self.h, nbins, hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                            ctypes.byref(top)), "table_spectrum")
+        return hist, top.value
+
+    def table_extract_device(self, lo=1, hi=0):
+        """(d_keys, d_counts, n): the A/C/G/T Map keys with lo <= value <= hi
+        (hi 0: no upper bound), sorted by key bytes, in device memory the
+        library owns -- n * k key bytes and n uint64 values, valid until the
+        next extract, reset or close.  Single-device contexts only."""
+        k, c, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(LIB.kmer_table_extract_device(self.h, lo, hi, ctypes.byref(k), ctypes.byref(c), ctypes.byref(n)),
+                    "table_extract_device")
+        return k.value or 0, c.value or 0, n.value
+
+    def table_extract(self, lo=1, hi=0) -> Result:
+        """The rows of the host result with lo <= value <= hi (hi 0: no upper
+        bound), record keys included, in its order (by key bytes)."""
+        r = ctypes.c_void_p()
+        self._check(LIB.kmer_table_extract(self.h, lo, hi, ctypes.byref(r)), "table_extract")
+        return Result(r)
 
     def table_exchange_prepare(self, world):
         """Table mode across ranks: (d_send, counts, parts) -- this session's

@@ -282,6 +282,9 @@ kmer_status kmer_close(kmer_ctx *c) {
     c->tlk_keys.release();
     c->tlk_cnt.release();
     c->tlk_bad.release();
+    c->tab_hist.release();
+    for (auto *b : {&c->tex_code, &c->tex_code2, &c->tex_val, &c->tex_val2}) b->release();
+    c->tex_keys.release();
     c->gm_keys.release();
     c->gm_keys2.release();
     for (auto *b : {&c->gm_cnt, &c->gm_cnt2, &c->gm_first, &c->gm_first2, &c->gm_h1, &c->gm_h2, &c->gm_h1b, &c->gm_h2b})
@@ -953,6 +956,271 @@ kmer_status kmer_table_routes(kmer_ctx *c, uint64_t *p1_fixed, uint64_t *p1_merg
     if (p1_merged) *p1_merged = m;
     if (p1_counted) *p1_counted = n;
     if (p2_fixed) *p2_fixed = f2;
+    return KMER_OK;
+}
+
+// ---- table spectrum and extraction (kmer_abundance.hip) ----
+static_assert(KMER_SPECTRUM_REG_MAX == AB_REGS && KMER_SPECTRUM_LDS_BINS == AB_LDS_BINS &&
+                  KMER_SPECTRUM_MAX_BINS == AB_HIST_BINS,
+              "include/kmer_api.h names the spectrum kernel's tiers");
+
+// the record keys as the host result lists them (build_table_result): (key, value)
+static std::vector<std::pair<std::string, uint64_t>> record_rows(const kmer_ctx *c) {
+    std::vector<std::pair<std::string, uint64_t>> out;
+    if (c->p.flags & KMER_FLAG_CANONICAL) {
+        for (auto &kv : canonical_records(c))
+            if (kv.first.compare(0, c->prefix.size(), c->prefix) == 0) out.emplace_back(kv.first, kv.second);
+    } else {
+        for (auto &kv : c->exotic) out.emplace_back(kv.first, kv.second.count);
+    }
+    return out;
+}
+
+// The error word after a walk of the table (read back by the caller with the
+// refused bucket): ERR_TAB_LOOKUP / ERR_TAB_EXTRACT are reported and cleared.
+static kmer_status abund_errors(kmer_ctx *c, uint32_t e, uint32_t q, const char *what) {
+    if (!(e & (ERR_TAB_LOOKUP | ERR_TAB_EXTRACT))) return KMER_OK;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)(e & ~(ERR_TAB_LOOKUP | ERR_TAB_EXTRACT)), 1, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (e & ERR_TAB_LOOKUP)
+        return fail(c, KMER_E_DEVICE, std::string(what) + ": the extent of bucket " + std::to_string(q) + " lies past the table");
+    return fail(c, KMER_E_DEVICE, std::string(what) + ": more keys written than counted");
+}
+
+// the table's view and the scratch words behind the device histogram
+static kmer_status abund_view(kmer_ctx *c, TabAbund *a) {
+    memset(a, 0, sizeof(*a));
+    const kmer_status vs = fill_view(c, a);
+    if (vs) return vs;
+    if (c->tab_hist.ensure(AB_HIST_BINS + 4, c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, KMER_E_OOM, "device allocation failed (spectrum histogram)");
+    }
+    a->hist = c->tab_hist.p;
+    a->n_out = c->tab_hist.p + AB_HIST_BINS + 2;
+    return KMER_OK;
+}
+
+// one context's spectrum added to hist (nbins bins, the last one open) and *top
+static kmer_status spectrum_one(kmer_ctx *c, uint32_t nbins, uint64_t *hist, uint64_t *top) {
+    auto add = [&](uint64_t v, uint64_t w) {
+        if (!v || !w) return;
+        if (v >= nbins - 1) {
+            hist[nbins - 1] += w;
+            *top += v * w;
+        } else {
+            hist[v] += w;
+        }
+    };
+    if (c->t_keys) {
+        if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+        hipStream_t s = c->stream;
+        TabAbund a;
+        const kmer_status vs = abund_view(c, &a);
+        if (vs) return vs;
+        unsigned long long *tail = c->tab_hist.p + AB_HIST_BINS;
+        HIPCHK(c, hipMemsetAsync(a.hist, 0, (AB_HIST_BINS + 4) * 8, s));
+        HIPCHK(c, launch_tab_spectrum(a, s));
+        HIPCHK(c, launch_tab_spectrum_tail(a.hist, nbins - 1, tail, s));
+        std::vector<uint64_t> part(nbins - 1);
+        std::vector<TabBig> big(a.n_big);
+        uint64_t last[2] = {0, 0};
+        uint32_t e = 0, q = 0;
+        HIPCHK(c, hipMemcpyAsync(part.data(), a.hist, part.size() * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(last, tail, 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&q, c->tlk_bad.p, 4, hipMemcpyDeviceToHost, s));
+        if (!big.empty())
+            HIPCHK(c, hipMemcpyAsync(big.data(), a.big, big.size() * sizeof(TabBig), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        const kmer_status es = abund_errors(c, e, q, "table spectrum");
+        if (es) return es;
+        for (uint32_t v = 0; v + 1 < nbins; ++v) hist[v] += part[v];
+        hist[nbins - 1] += last[0];
+        *top += last[1];
+        for (const TabBig &b : big) {                // (entries hold TAB_CMAX: the kernel skipped them)
+            uint64_t keys[2];
+            bool dbl;
+            const uint32_t w = tab_entry_keys(b.h, a.k, a.plo, a.phi, a.pmask, a.canonical != 0, keys, &dbl);
+            add(dbl ? 2 * b.count : b.count, w);
+        }
+    }
+    for (auto &kv : record_rows(c)) add(kv.second, 1);
+    return KMER_OK;
+}
+
+kmer_status kmer_table_spectrum(kmer_ctx *c, uint32_t nbins, uint64_t *hist, uint64_t *top_sum) {
+    if (!c || !hist || nbins < 2 || nbins > KMER_SPECTRUM_MAX_BINS) return KMER_E_BAD_PARAM;
+    uint64_t top = 0;
+    if (!c->group.empty()) {                         // a group: disjoint classes, the records in child 0
+        if (c->mode != MODE_TABLE || !c->t_done) return fail(c, KMER_E_STATE, "no table finish on this group yet");
+        std::fill(hist, hist + nbins, 0);
+        for (kmer_ctx *x : c->group) {
+            if (hipSetDevice(x->device) != hipSuccess) return KMER_E_DEVICE;
+            const kmer_status st = settle(x);
+            if (st) return fail(c, st, x->err);
+            const kmer_status ss = spectrum_one(x, nbins, hist, &top);
+            if (ss) return fail(c, ss, x->err);
+        }
+        if (top_sum) *top_sum = top;
+        return KMER_OK;
+    }
+    SETTLE(c);
+    const kmer_status st = lookup_state(c);
+    if (st) return st;
+    std::fill(hist, hist + nbins, 0);
+    const kmer_status ss = spectrum_one(c, nbins, hist, &top);
+    if (ss) return ss;
+    if (top_sum) *top_sum = top;
+    return KMER_OK;
+}
+
+// The device extract of one context: n keys of k bytes at *keys, their values
+// at *counts, sorted by key bytes; complete when this returns.
+static kmer_status extract_run(kmer_ctx *c, uint64_t lo, uint64_t hi, const uint8_t **keys, const uint64_t **counts,
+                               uint64_t *n_out) {
+    *keys = nullptr;
+    *counts = nullptr;
+    *n_out = 0;
+    if (lo == 0) lo = 1;
+    if ((hi && hi < lo) || !c->t_keys) return KMER_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    hipStream_t s = c->stream;
+    const uint32_t k = c->p.k, cus = (uint32_t)std::max(c->n_cu, 1);
+    TabAbund a;
+    const kmer_status vs = abund_view(c, &a);
+    if (vs) return vs;
+    a.lo = lo;
+    a.hi = hi ? hi : ~0ull;
+    uint64_t n = 0;
+    uint32_t e = 0, q = 0;
+    HIPCHK(c, hipMemsetAsync(a.n_out, 0, 8, s));
+    HIPCHK(c, launch_tab_extract_count(a, s));
+    HIPCHK(c, hipMemcpyAsync(&n, a.n_out, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&q, c->tlk_bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    kmer_status es = abund_errors(c, e, q, "table extract");
+    if (es || !n) return es;
+    size_t tmp_bytes = 0;
+    HIPCHK(c, tab_extract_sort_bytes(n, k, &tmp_bytes));
+    bool ok = c->tmp.ensure(tmp_bytes + 16, s) == hipSuccess && c->tex_keys.ensure(n * k + 4, s) == hipSuccess;
+    for (auto *b : {&c->tex_code, &c->tex_code2, &c->tex_val, &c->tex_val2}) ok = ok && b->ensure(n, s) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(c, KMER_E_OOM, "device allocation failed (" + std::to_string(n) + " extracted keys)");
+    }
+    a.cap_out = n;
+    a.codes = c->tex_code.p;
+    a.vals = c->tex_val.p;
+    const uint64_t *sc = nullptr, *sv = nullptr;
+    uint64_t wrote = 0;
+    HIPCHK(c, hipMemsetAsync(a.n_out, 0, 8, s));
+    HIPCHK(c, launch_tab_extract_write(a, s));
+    HIPCHK(c, launch_tab_extract_sort(c->tex_code.p, c->tex_code2.p, c->tex_val.p, c->tex_val2.p, n, k, c->tmp.p,
+                                      tmp_bytes, &sc, &sv, s));
+    HIPCHK(c, launch_tab_extract_decode(sc, n, k, c->tex_keys.p, cus, s));
+    HIPCHK(c, hipMemcpyAsync(&wrote, a.n_out, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&q, c->tlk_bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    es = abund_errors(c, e, q, "table extract");
+    if (es) return es;
+    if (wrote != n) return fail(c, KMER_E_DEVICE, "table extract: counted and written keys differ");
+    *keys = c->tex_keys.p;
+    *counts = sv;
+    *n_out = n;
+    return KMER_OK;
+}
+
+kmer_status kmer_table_extract_device(kmer_ctx *c, uint64_t lo, uint64_t hi, const void **d_keys, const void **d_counts,
+                                      uint64_t *n) {
+    if (!c || !d_keys || !d_counts || !n) return KMER_E_BAD_PARAM;
+    SETTLE(c);
+    const kmer_status st = lookup_state(c);
+    if (st) return st;
+    const uint8_t *dk = nullptr;
+    const uint64_t *dc = nullptr;
+    const kmer_status es = extract_run(c, lo, hi, &dk, &dc, n);
+    *d_keys = dk;
+    *d_counts = dc;
+    return es;
+}
+
+// One context's rows with a value in range, sorted by key bytes: the device
+// extract copied to the host, the record keys merged in.
+static kmer_status extract_rows(kmer_ctx *c, uint64_t lo, uint64_t hi, std::vector<std::pair<std::string, uint64_t>> &rows) {
+    const uint8_t *dk = nullptr;
+    const uint64_t *dc = nullptr;
+    uint64_t n = 0;
+    const kmer_status es = extract_run(c, lo, hi, &dk, &dc, &n);
+    if (es) return es;
+    const uint64_t k = c->p.k;
+    std::vector<char> kb(n * k);
+    std::vector<uint64_t> cnt(n);
+    if (n) {
+        hipStream_t s = c->stream;
+        HIPCHK(c, hipMemcpyAsync(kb.data(), dk, n * k, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), dc, n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (lo == 0) lo = 1;
+    std::vector<std::pair<std::string, uint64_t>> recs;
+    for (auto &kv : record_rows(c))
+        if (kv.second >= lo && (hi == 0 || kv.second <= hi)) recs.push_back(kv);
+    std::sort(recs.begin(), recs.end());
+    rows.clear();
+    rows.reserve(n + recs.size());
+    size_t j = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const char *x = kb.data() + i * k;
+        while (j < recs.size() && recs[j].first.compare(0, std::string::npos, x, k) < 0) rows.push_back(recs[j++]);
+        rows.emplace_back(std::string(x, k), cnt[i]);
+    }
+    while (j < recs.size()) rows.push_back(recs[j++]);
+    return KMER_OK;
+}
+
+kmer_status kmer_table_extract(kmer_ctx *c, uint64_t lo, uint64_t hi, kmer_result **out) {
+    if (!c || !out) return KMER_E_BAD_PARAM;
+    std::vector<std::pair<std::string, uint64_t>> rows;
+    uint64_t lines = 0;
+    if (!c->group.empty()) {                         // a group: the children's key sets are disjoint
+        if (c->mode != MODE_TABLE || !c->t_done) return fail(c, KMER_E_STATE, "no table finish on this group yet");
+        std::vector<std::pair<std::string, uint64_t>> part;
+        for (kmer_ctx *x : c->group) {
+            if (hipSetDevice(x->device) != hipSuccess) return KMER_E_DEVICE;
+            kmer_status st = settle(x);
+            if (!st) st = extract_rows(x, lo, hi, part);
+            if (st) return fail(c, st, x->err);
+            const size_t mid = rows.size();
+            rows.insert(rows.end(), part.begin(), part.end());
+            std::inplace_merge(rows.begin(), rows.begin() + mid, rows.end());
+        }
+        lines = c->t_lines;
+    } else {
+        SETTLE(c);
+        kmer_status st = lookup_state(c);
+        if (st) return st;
+        if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+        st = extract_rows(c, lo, hi, rows);
+        if (st) return st;
+        StreamPos pos;
+        st = read_pos(c, &pos);
+        if (st) return st;
+        lines = c->fasta ? c->fa_lines : pos.lines + pos.ends_open;
+    }
+    kmer_result *r = new (std::nothrow) kmer_result();
+    if (!r) return fail(c, KMER_E_OOM, "host allocation failed");
+    r->lines = lines;
+    for (auto &e : rows) {
+        r->keys.insert(r->keys.end(), e.first.begin(), e.first.end());
+        r->offsets.push_back(r->keys.size());
+        r->counts.push_back(e.second);
+        r->firsts.push_back(0);
+    }
+    *out = r;
     return KMER_OK;
 }
 

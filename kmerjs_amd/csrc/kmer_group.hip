@@ -317,6 +317,7 @@ kmer_status group_count(kmer_ctx *g, GroupSrc &src, kmer_result **out) {
     });
     if (st) return st;
     g->t_done = true;
+    g->t_lines = total_lines;
     uint64_t keys = 0;
     for (size_t o = 0; o < N; ++o) {
         uint64_t kk = 0;

@@ -266,6 +266,11 @@ struct kmer_ctx {
     DBuf<uint8_t> tlk_keys;        // table lookup (host call): one piece of uploaded query keys ...
     DBuf<uint64_t> tlk_cnt;        // ... and its counts
     DBuf<uint32_t> tlk_bad;        // table lookup: a bucket whose extent was refused (ERR_TAB_LOOKUP)
+    // table spectrum / extract (kmer_abundance.hip): scratch that persists across calls
+    DBuf<unsigned long long> tab_hist;   // spectrum: AB_HIST_BINS bins, then [0..1] the last bin, [2] extract count / cursor
+    DBuf<uint64_t> tex_code, tex_code2, tex_val, tex_val2;   // extract: (2-bit code, value) pairs and the sort's twins
+    DBuf<uint8_t> tex_keys;        // extract: the sorted keys' bytes (valid until the next extract)
+    uint64_t t_lines = 0;          // a group: the input lines of its last count (kmer_table_extract)
     hipEvent_t tev[8] = {};        // table phase events
     // multi-device group (kmer_params.ndev > 1): one child context per device;
     // the group itself owns no device state beyond the merge buffers on

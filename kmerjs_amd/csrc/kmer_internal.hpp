@@ -48,6 +48,7 @@ enum : uint32_t {
     ERR_BKT_CAP = 1u << 12,          // bucket finish: a run past its bucket's fixed region (counted route redoes it)
     ERR_BKT_RANK = 1u << 13,         // bucket finish: a partitioned rank past the hits (a defect)
     ERR_TAB_LOOKUP = 1u << 14,       // table lookup: a bucket extent past the table (not read; a defect)
+    ERR_TAB_EXTRACT = 1u << 15,      // table extract: a slot past the counted keys (not written; a defect)
     // not an error: a tile without '\n' had hits, or a tile overflowed its hit
     // slots -- cross segments may be long (finish sorts the whole cross list)
     INFO_LONGSEG = 1u << 16,
@@ -605,6 +606,50 @@ __host__ __device__ inline void tab_code2_planar(uint64_t code2, uint32_t k, uin
     *cf = ((uint64_t)hi << k) | lo;
     *cr = tab_rc_code(*cf, k);
 }
+// Key arithmetic of the table's by-value readers (kmer_abundance.hip): from a
+// table entry to the Map keys it stands for, and from a planar code back to
+// the matcher's 2-bit code.
+__host__ __device__ inline uint64_t tab_spread_bits(uint32_t x) {   // bit m of x at bit 2 m (tab_even_bits' inverse)
+    uint64_t v = x;
+    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
+    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
+    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    v = (v | (v << 2)) & 0x3333333333333333ull;
+    v = (v | (v << 1)) & 0x5555555555555555ull;
+    return v;
+}
+// planar code -> 2-bit code, first base most significant (tab_code2_planar's
+// inverse): 2-bit codes compare as the key bytes do (A < C < G < T)
+__host__ __device__ inline uint64_t tab_planar_code2(uint64_t code, uint32_t k) {
+    const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+    const uint32_t lo = (uint32_t)code & km, hi = (uint32_t)(code >> k) & km;
+    const uint32_t rlo = __builtin_bitreverse32(lo) >> (32 - k), rhi = __builtin_bitreverse32(hi) >> (32 - k);
+    return tab_spread_bits(rlo) | (tab_spread_bits(rhi) << 1);
+}
+// The Map keys of the table entry h (the loop body of build_table_result):
+// their planar codes in keys[0 .. n), n = 0, 1 or 2 the return value; *dbl:
+// the value is twice the entry's count (table mode, x == rc x).  Table mode:
+// x and rc x, each if it starts with the prefix (one key when x == rc x);
+// canonical mode: the smaller string of the class, if it starts with the prefix.
+__host__ __device__ inline uint32_t tab_entry_keys(uint64_t h, uint32_t k, uint32_t plo, uint32_t phi, uint32_t pmask,
+                                                   bool canonical, uint64_t keys[2], bool *dbl) {
+    const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+    const uint64_t x = tab_code(h, k, k <= TAB_NARROW_K, TAB_INV), r = tab_rc_code(x, k);
+    const bool okx = (((((uint32_t)x & km) ^ plo) | (((uint32_t)(x >> k) & km) ^ phi)) & pmask) == 0;
+    const bool okr = (((((uint32_t)r & km) ^ plo) | (((uint32_t)(r >> k) & km) ^ phi)) & pmask) == 0;
+    *dbl = false;
+    if (canonical) {
+        const bool fx = tab_str_le(x, r, k);
+        keys[0] = fx ? x : r;
+        return (fx ? okx : okr) ? 1u : 0u;
+    }
+    const bool pal = x == r;
+    *dbl = pal;
+    uint32_t n = 0;
+    if (okx) keys[n++] = x;
+    if (!pal && okr) keys[n++] = r;
+    return n;
+}
 // the hash the table digest weighs: tab_mix(min(code(w), code(rc w))) for every k
 __host__ __device__ inline uint64_t tab_digest_key(uint64_t h, uint32_t k, bool narrow) {
     if (!narrow) return h;
@@ -786,6 +831,36 @@ struct TabProbe : TabView {
 };
 hipError_t tab_probe_temp_bytes(uint64_t m, size_t *bytes);
 hipError_t launch_tab_probe(const TabProbe &a, uint32_t n_cu, hipStream_t s);
+// The by-value readers of a finished table (kmer_abundance.hip).  Spectrum:
+// hist[v] += the Map keys with value v, over the entries whose count is in
+// the 20-bit field (the host adds the big list and the record keys); counts
+// 1 .. AB_REGS are kept in registers, counts below AB_LDS_BINS in LDS.
+// Extract: the Map keys with lo <= value <= hi as (2-bit code, value) pairs,
+// first counted (n_out = their number), then written at codes / vals in no
+// order (n_out = the cursor, cap_out = the counted number), sorted by code
+// and decoded to key bytes.
+constexpr uint32_t AB_REGS = 4;
+constexpr uint32_t AB_LDS_BINS = 4096;
+constexpr uint32_t AB_HIST_BINS = 1u << 21;            // every value of a 20-bit count, doubled
+struct TabAbund : TabView {
+    unsigned long long *hist;      // spectrum: AB_HIST_BINS bins, zeroed by the caller
+    uint64_t lo, hi;               // extract: the range, both ends included
+    unsigned long long *n_out;
+    uint64_t cap_out;
+    uint64_t *codes, *vals;
+};
+hipError_t launch_tab_spectrum(const TabAbund &a, hipStream_t s);
+// out[0] = sum of hist[from ..), out[1] = sum of v hist[v] over the same bins (out zeroed by the caller)
+hipError_t launch_tab_spectrum_tail(const unsigned long long *hist, uint32_t from, unsigned long long *out,
+                                    hipStream_t s);
+hipError_t launch_tab_extract_count(const TabAbund &a, hipStream_t s);
+hipError_t launch_tab_extract_write(const TabAbund &a, hipStream_t s);
+hipError_t tab_extract_sort_bytes(uint64_t n, uint32_t k, size_t *bytes);
+hipError_t launch_tab_extract_sort(uint64_t *codes, uint64_t *codes2, uint64_t *vals, uint64_t *vals2, uint64_t n,
+                                   uint32_t k, void *tmp, size_t tmp_bytes, const uint64_t **sorted_codes,
+                                   const uint64_t **sorted_vals, hipStream_t s);
+hipError_t launch_tab_extract_decode(const uint64_t *codes, uint64_t n, uint32_t k, uint8_t *keys, uint32_t n_cu,
+                                     hipStream_t s);
 // multi-GPU table exchange: copy n segments {src offset, dst offset, length}
 // of u64 keys (one workgroup per segment, grid-strided)
 struct TabSeg {

@@ -343,13 +343,19 @@ class KmerFinder:
             if own:
                 match.close()
 
-    def find_matches_table(self, counter, query_size=None, with_removed=False):
+    def find_matches_table(self, counter, query_size=None, with_removed=False, min_count=1):
         """findMatches with a table-mode count as the query (a Counter opened
         with FLAG_UNORDERED / FLAG_CANONICAL, after its finish): the join runs
         on the device against the counter's table.  query_size defaults to the
         table's distinct Map keys (the kmerMapSize of the Map the table stands
         for).  Returns the summaries; with_removed (method 'winner'): (summaries,
-        the k-mers the winners took out of the query, as bytes, ascending)."""
+        the k-mers the winners took out of the query, as bytes, ascending).
+        min_count > 1: the query is the Map's keys of value >= min_count (the
+        reference's `v >= coverage`, lib/index.js:190), extracted on the device
+        (Counter.table_extract_device) and joined as a device result;
+        query_size then defaults to their number."""
+        if min_count > 1:
+            return self._find_matches_extract(counter, query_size, with_removed, min_count)
         if query_size is None:
             query_size = counter.table_stats()[1]
         m = Match(self.db, table=counter)
@@ -361,6 +367,33 @@ class KmerFinder:
             return out, self._kmers_at(idx)
         finally:
             m.close()
+
+    def _find_matches_extract(self, counter, query_size, with_removed, min_count):
+        d_keys, d_counts, n = counter.table_extract_device(min_count)
+        if query_size is None:
+            query_size = n
+        m = Match(self.db, device_result=(d_keys, counter.k, d_counts, n))
+        try:
+            out = self.find_matches(None, query_size, match=m)
+            if not with_removed:
+                return out
+            idx = np.nonzero(m.removed())[0] if self.method == "winner" else []
+            return out, self._extracted_at(d_keys, counter.k, idx)
+        finally:
+            m.close()
+
+    @staticmethod
+    def _extracted_at(d_keys, k, idx):
+        """The extracted keys (k bytes each at d_keys, device memory) at ascending indices."""
+        import torch
+        from .multi import _CudaArray
+        if len(idx) == 0:
+            return []
+        lo, hi = int(idx[0]), int(idx[-1]) + 1
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rows = torch.as_tensor(_CudaArray(d_keys + lo * k, (hi - lo) * k, "|u1"), device=dev).cpu().numpy()
+        rows = rows.reshape(hi - lo, k)
+        return [rows[int(i) - lo].tobytes() for i in idx]
 
     def _kmers_at(self, idx):
         """DB k-mers at ascending indices, decoded in runs of neighbours."""
