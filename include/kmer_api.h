@@ -332,6 +332,74 @@ kmer_status kmer_table_spectrum(kmer_ctx *ctx, uint32_t nbins, uint64_t *hist, u
 kmer_status kmer_table_extract_device(kmer_ctx *ctx, uint64_t lo, uint64_t hi, const void **d_keys,
                                       const void **d_counts, uint64_t *n);
 kmer_status kmer_table_extract(kmer_ctx *ctx, uint64_t lo, uint64_t hi, kmer_result **out);
+/* Two tables related to each other (both after a table finish, until the next
+ * reset of either; the calls may be repeated and interleaved with stats,
+ * digest, lookup, spectrum, extract and match, and leave both tables
+ * unchanged).  "The Map of A" is the Map context a's host result describes,
+ * as above; a key is IN A iff its value there is >= max(min_a, 1), IN B
+ * likewise with min_b.  The two contexts have the same k, mode and prefix, so
+ * a class {x, rc x} has the same Map keys (and the same doubling) on both
+ * sides: the tables are joined on the class, bucket by bucket (equal k: equal
+ * hash, bucket q of A meets bucket q of B only), on the device in LDS.  A
+ * count field of 0xFFFFF resolves through that side's big list.  a == b is
+ * legal.
+ *
+ * KMER_JOIN_TILE: the entries of one bucket a wave stages in LDS at a time (a
+ * longer bucket is split by leading remainder bits and both sides are re-read
+ * per part).
+ *
+ * kmer_table_overlap: keys_a / keys_b = the distinct Map keys in A / in B,
+ * keys_both = the keys in both; total_a / total_b = the sum of the values of
+ * the keys in A / in B; shared_a / shared_b = the sum of A's / of B's values
+ * over the keys in both; sum_min = the sum of min(vA, vB) over the keys in
+ * both.  (Jaccard = keys_both / (keys_a + keys_b - keys_both), containment of
+ * A = keys_both / keys_a, Bray-Curtis = 1 - 2 sum_min / (total_a + total_b).)
+ *
+ * kmer_table_compare: *out filled, record keys (a byte outside A/C/G/T; they
+ * live on the host) included as kmer_table_stats includes them: with min_a =
+ * min_b = 1, keys_a and total_a are the keys and total of kmer_table_stats(a),
+ * keys_b and total_b those of b.  The ranks' structs of two tables exchanged
+ * with the same world and rank add up.
+ *
+ * KMER_SETOP_*: INTERSECT = the keys in A and in B, value min(vA, vB);
+ * SUBTRACT = the keys in A and not in B, value vA; UNION = the keys in A or
+ * in B, value = the sum of the values of the sides the key is in.
+ *
+ * kmer_table_setop_device: the A/C/G/T keys of the operation's result sorted
+ * ascending by key bytes: *d_keys = n * k key bytes back to back, *d_counts =
+ * n uint64 values, library-owned device memory of context a (the extract's
+ * buffers), complete when the call returns and valid until the next extract,
+ * setop, reset or close on a (kmer_match_open_device takes them as they are).
+ * The buffers are sized from a counting pass; KMER_E_OOM leaves both contexts
+ * usable.  Exchanged tables (same world and rank) give their share: the
+ * ranks' results are disjoint.
+ *
+ * kmer_table_setop: the host twin, a result in the host result's order (by
+ * key bytes), with the record keys of the two contexts joined by the same
+ * rules and merged in; its lines are those of a.
+ *
+ * The work runs on a's stream, which waits for the work queued on b's; a
+ * chunk in flight on either context is settled first.  The call uses both
+ * contexts: neither may be in use on another thread.  Checked before any
+ * device call: KMER_E_BAD_PARAM for NULL contexts or out-pointers, op >
+ * KMER_SETOP_UNION, contexts on different devices, or contexts that differ in
+ * k, KMER_FLAG_CANONICAL or prefix bytes; KMER_E_STATE for a group context
+ * (ndev > 1), a context not in table mode, or one without a table finish.
+ * KMER_E_DEVICE, naming the bucket and the context, if a bucket's extent lies
+ * past its table (it is not read). */
+#define KMER_JOIN_TILE 1024u
+typedef struct {
+    uint64_t keys_a, keys_b, keys_both;   /* distinct Map keys in A, in B, in both            */
+    uint64_t total_a, total_b;            /* sum of their values                              */
+    uint64_t shared_a, shared_b;          /* sum of A's / of B's values over the keys in both */
+    uint64_t sum_min;                     /* sum of min(vA, vB) over the keys in both         */
+} kmer_table_overlap;
+kmer_status kmer_table_compare(kmer_ctx *a, kmer_ctx *b, uint64_t min_a, uint64_t min_b, kmer_table_overlap *out);
+enum { KMER_SETOP_INTERSECT = 0, KMER_SETOP_SUBTRACT = 1, KMER_SETOP_UNION = 2 };
+kmer_status kmer_table_setop_device(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
+                                    const void **d_keys, const void **d_counts, uint64_t *n);
+kmer_status kmer_table_setop(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
+                             kmer_result **out);
 /* The table itself, in device memory (to read counts, use kmer_table_lookup,
  * which owns the two key encodings below; this is the raw layout for a
  * consumer that walks the whole table; the library's own are

@@ -29,6 +29,12 @@ TAB_PARTS = 1024    # table mode: pass-1 partitions (ownership unit across ranks
 SPECTRUM_REG_MAX = 4
 SPECTRUM_LDS_BINS = 4096
 SPECTRUM_MAX_BINS = 1 << 21
+# kmer_table_setop* (include/kmer_api.h, KMER_SETOP_* / KMER_JOIN_TILE): the operations, and the
+# entries of one bucket a wave of the join kernel stages in LDS at a time
+SETOP_INTERSECT = 0
+SETOP_SUBTRACT = 1
+SETOP_UNION = 2
+JOIN_TILE = 1024
 WRITE_JSON = 0      # JSON.stringify(mapToJSON(map)), lib/kmers.js:46-54
 WRITE_LEGACY = 1    # "{\nkey: count,...}\n", lib/index.js:381-388
 
@@ -44,6 +50,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
            "kmer_table_lookup", "kmer_table_lookup_device",
            "kmer_table_spectrum", "kmer_table_extract_device", "kmer_table_extract",
+           "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
 MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_kmers", "kmer_db_close", "kmer_match_open",
@@ -59,6 +66,12 @@ class Winner(ctypes.Structure):
     _fields_ = [("tmpl", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("uscore", ctypes.c_uint64),
                 ("tscore", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("first_uscore", ctypes.c_uint64),
                 ("first_tscore", ctypes.c_uint64)]
+
+
+class TableOverlap(ctypes.Structure):
+    """kmer_table_overlap (kmer_table_compare)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("keys_a", "keys_b", "keys_both", "total_a", "total_b",
+                                                      "shared_a", "shared_b", "sum_min")]
 
 
 class Params(ctypes.Structure):
@@ -140,6 +153,10 @@ def _load():
         "kmer_table_spectrum": (ctypes.c_int, [vp, ctypes.c_uint32, pu64, pu64]),
         "kmer_table_extract_device": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp), ctypes.POINTER(vp), pu64]),
         "kmer_table_extract": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp)]),
+        "kmer_table_compare": (ctypes.c_int, [vp, vp, u64, u64, ctypes.POINTER(TableOverlap)]),
+        "kmer_table_setop_device": (ctypes.c_int, [vp, vp, ctypes.c_uint32, u64, u64, ctypes.POINTER(vp),
+                                                   ctypes.POINTER(vp), pu64]),
+        "kmer_table_setop": (ctypes.c_int, [vp, vp, ctypes.c_uint32, u64, u64, ctypes.POINTER(vp)]),
         "kmer_status_string": (ctypes.c_char_p, [ctypes.c_int]),
         "kmer_last_error": (ctypes.c_char_p, [vp]),
         "kmer_version": (ctypes.c_char_p, []),
@@ -467,6 +484,38 @@ class Counter:
         bound), record keys included, in its order (by key bytes)."""
         r = ctypes.c_void_p()
         self._check(LIB.kmer_table_extract(self.h, lo, hi, ctypes.byref(r)), "table_extract")
+        return Result(r)
+
+    def table_compare(self, other, min_a=1, min_b=1):
+        """This table (A) and another Counter's (B; same k, mode and prefix,
+        same device) compared on the device: the eight fields of
+        kmer_table_overlap over the Map keys in A (value >= min_a) and in B
+        (value >= min_b), record keys included, plus jaccard = keys_both /
+        |A or B| and containment_a = keys_both / keys_a (0.0 when undefined)."""
+        o = TableOverlap()
+        self._check(LIB.kmer_table_compare(self.h, other.h, min_a, min_b, ctypes.byref(o)), "table_compare")
+        out = {name: int(getattr(o, name)) for name, _ in TableOverlap._fields_}
+        either = out["keys_a"] + out["keys_b"] - out["keys_both"]
+        out["jaccard"] = out["keys_both"] / either if either else 0.0
+        out["containment_a"] = out["keys_both"] / out["keys_a"] if out["keys_a"] else 0.0
+        return out
+
+    def table_setop_device(self, other, op, min_a=1, min_b=1):
+        """(d_keys, d_counts, n): SETOP_INTERSECT / SETOP_SUBTRACT /
+        SETOP_UNION of this table's Map (A) and another Counter's (B), A/C/G/T
+        keys only, sorted by key bytes, in device memory this context owns --
+        n * k key bytes and n uint64 values, valid until the next extract,
+        setop, reset or close on this context."""
+        k, c, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(LIB.kmer_table_setop_device(self.h, other.h, op, min_a, min_b, ctypes.byref(k), ctypes.byref(c),
+                                                ctypes.byref(n)), "table_setop_device")
+        return k.value or 0, c.value or 0, n.value
+
+    def table_setop(self, other, op, min_a=1, min_b=1) -> Result:
+        """The set operation as a host result: rows by key bytes, the two
+        contexts' record keys joined by the same rules and merged in."""
+        r = ctypes.c_void_p()
+        self._check(LIB.kmer_table_setop(self.h, other.h, op, min_a, min_b, ctypes.byref(r)), "table_setop")
         return Result(r)
 
     def table_exchange_prepare(self, world):

@@ -285,6 +285,7 @@ kmer_status kmer_close(kmer_ctx *c) {
     c->tab_hist.release();
     for (auto *b : {&c->tex_code, &c->tex_code2, &c->tex_val, &c->tex_val2}) b->release();
     c->tex_keys.release();
+    c->tjoin.release();
     c->gm_keys.release();
     c->gm_keys2.release();
     for (auto *b : {&c->gm_cnt, &c->gm_cnt2, &c->gm_first, &c->gm_first2, &c->gm_h1, &c->gm_h2, &c->gm_h1b, &c->gm_h2b})
@@ -1148,6 +1149,24 @@ kmer_status kmer_table_extract_device(kmer_ctx *c, uint64_t lo, uint64_t hi, con
     return es;
 }
 
+// rows = the n sorted A/C/G/T keys (k bytes each in kb, values in cnt) and the
+// record keys recs, merged by key bytes
+static void merge_rows(const std::vector<char> &kb, const std::vector<uint64_t> &cnt, uint64_t k,
+                       std::vector<std::pair<std::string, uint64_t>> &recs,
+                       std::vector<std::pair<std::string, uint64_t>> &rows) {
+    const uint64_t n = cnt.size();
+    std::sort(recs.begin(), recs.end());
+    rows.clear();
+    rows.reserve(n + recs.size());
+    size_t j = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const char *x = kb.data() + i * k;
+        while (j < recs.size() && recs[j].first.compare(0, std::string::npos, x, k) < 0) rows.push_back(recs[j++]);
+        rows.emplace_back(std::string(x, k), cnt[i]);
+    }
+    while (j < recs.size()) rows.push_back(recs[j++]);
+}
+
 // One context's rows with a value in range, sorted by key bytes: the device
 // extract copied to the host, the record keys merged in.
 static kmer_status extract_rows(kmer_ctx *c, uint64_t lo, uint64_t hi, std::vector<std::pair<std::string, uint64_t>> &rows) {
@@ -1169,16 +1188,7 @@ static kmer_status extract_rows(kmer_ctx *c, uint64_t lo, uint64_t hi, std::vect
     std::vector<std::pair<std::string, uint64_t>> recs;
     for (auto &kv : record_rows(c))
         if (kv.second >= lo && (hi == 0 || kv.second <= hi)) recs.push_back(kv);
-    std::sort(recs.begin(), recs.end());
-    rows.clear();
-    rows.reserve(n + recs.size());
-    size_t j = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        const char *x = kb.data() + i * k;
-        while (j < recs.size() && recs[j].first.compare(0, std::string::npos, x, k) < 0) rows.push_back(recs[j++]);
-        rows.emplace_back(std::string(x, k), cnt[i]);
-    }
-    while (j < recs.size()) rows.push_back(recs[j++]);
+    merge_rows(kb, cnt, k, recs, rows);
     return KMER_OK;
 }
 
@@ -1214,6 +1224,265 @@ kmer_status kmer_table_extract(kmer_ctx *c, uint64_t lo, uint64_t hi, kmer_resul
     kmer_result *r = new (std::nothrow) kmer_result();
     if (!r) return fail(c, KMER_E_OOM, "host allocation failed");
     r->lines = lines;
+    for (auto &e : rows) {
+        r->keys.insert(r->keys.end(), e.first.begin(), e.first.end());
+        r->offsets.push_back(r->keys.size());
+        r->counts.push_back(e.second);
+        r->firsts.push_back(0);
+    }
+    *out = r;
+    return KMER_OK;
+}
+
+// ---- set operations of two tables (kmer_setops.hip) ----
+static_assert(KMER_JOIN_TILE == JOIN_TILE && (int)KMER_SETOP_INTERSECT == (int)JOIN_INTERSECT &&
+                  (int)KMER_SETOP_SUBTRACT == (int)JOIN_SUBTRACT && (int)KMER_SETOP_UNION == (int)JOIN_UNION,
+              "include/kmer_api.h names the join kernel's tile and operations");
+static_assert(sizeof(kmer_table_overlap) == 8 * sizeof(uint64_t), "kmer_table_overlap: the kernel's eight sums");
+
+static kmer_status table_view_impl(kmer_ctx *c, TabView *v, TabOwner *o);
+
+// The parameter and state checks of a call on two contexts: no device call yet.
+static kmer_status join_params(kmer_ctx *a, kmer_ctx *b) {
+    if (a->device != b->device) return fail(a, KMER_E_BAD_PARAM, "the two contexts are on different devices");
+    if (a->p.k != b->p.k || ((a->p.flags ^ b->p.flags) & KMER_FLAG_CANONICAL) || a->prefix != b->prefix)
+        return fail(a, KMER_E_BAD_PARAM, "the two contexts differ in k, KMER_FLAG_CANONICAL or prefix");
+    for (kmer_ctx *c : {a, b}) {
+        const char *who = c == a ? "first" : "second";
+        if (!c->group.empty()) return fail(a, KMER_E_STATE, std::string("single-device call: the ") + who + " context is a group");
+        if (c->mode != MODE_TABLE) return fail(a, KMER_E_STATE, std::string("the ") + who + " context is not in table mode");
+        if (!c->t_done) return fail(a, KMER_E_STATE, std::string("no table finish yet on the ") + who + " context");
+    }
+    return KMER_OK;
+}
+
+// Both contexts settled, their tables' views filled (an empty table: nd ==
+// nullptr), the scratch words of context a behind the outputs, and a's stream
+// ordered after the work queued on b's.  *empty: both tables are empty.
+static kmer_status join_views(kmer_ctx *a, kmer_ctx *b, uint64_t min_a, uint64_t min_b, TabJoin *j, bool *empty) {
+    memset(j, 0, sizeof(*j));
+    TabOwner oa, ob;
+    kmer_status st = table_view_impl(a, &j->a, &oa);
+    if (st) return st;
+    if (b != a) {
+        st = table_view_impl(b, &j->b, &ob);
+        if (st) return fail(a, st, "second context: " + b->err);
+    } else {
+        j->b = j->a;
+        ob = oa;
+    }
+    *empty = oa.empty && ob.empty;
+    if (*empty) return KMER_OK;
+    auto hollow = [](TabView *v, const TabView &from) {  // (the key parameters are the same on both sides)
+        *v = from;
+        v->ent = nullptr;
+        v->start = nullptr;
+        v->nd = nullptr;
+        v->big = nullptr;
+        v->n_big = 0;
+        v->cap = 0;
+    };
+    if (oa.empty) hollow(&j->a, j->b);
+    if (ob.empty) hollow(&j->b, j->a);
+    if (hipSetDevice(a->device) != hipSuccess) return fail(a, KMER_E_DEVICE, "hipSetDevice failed");
+    hipStream_t s = a->stream;
+    if (a->tlk_bad.ensure(2, s) != hipSuccess || a->tjoin.ensure(16, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(a, KMER_E_OOM, "device allocation failed (set operation scratch)");
+    }
+    j->min_a = std::max<uint64_t>(min_a, 1);
+    j->min_b = std::max<uint64_t>(min_b, 1);
+    j->sums = a->tjoin.p;
+    j->n_out = a->tjoin.p + 8;
+    j->err = a->d_err;
+    j->badq = a->tlk_bad.p;
+    if (b != a) {
+        HIPCHK(a, hipEventRecord(a->evw, b->stream));
+        HIPCHK(a, hipStreamWaitEvent(s, a->evw, 0));
+    }
+    return KMER_OK;
+}
+
+// The error word after a walk of the two tables (read back by the caller with
+// the refused bucket and its side): reported on context a and cleared.
+static kmer_status join_errors(kmer_ctx *a, uint32_t e, const uint32_t bad[2], const char *what) {
+    if (!(e & (ERR_TAB_LOOKUP | ERR_TAB_EXTRACT))) return KMER_OK;
+    hipStream_t s = a->stream;
+    HIPCHK(a, hipMemsetD32Async((hipDeviceptr_t)a->d_err, (int)(e & ~(ERR_TAB_LOOKUP | ERR_TAB_EXTRACT)), 1, s));
+    HIPCHK(a, hipStreamSynchronize(s));
+    if (e & ERR_TAB_LOOKUP)
+        return fail(a, KMER_E_DEVICE, std::string(what) + ": the extent of bucket " + std::to_string(bad[0]) + " of the " +
+                                          (bad[1] ? "second" : "first") + " context lies past the table");
+    return fail(a, KMER_E_DEVICE, std::string(what) + ": more keys written than counted");
+}
+
+// the record keys that are in a side (value >= max(min, 1))
+static std::unordered_map<std::string, uint64_t> join_records(const kmer_ctx *c, uint64_t min) {
+    std::unordered_map<std::string, uint64_t> out;
+    for (auto &kv : record_rows(c))
+        if (kv.second >= std::max<uint64_t>(min, 1)) out.emplace(kv.first, kv.second);
+    return out;
+}
+
+kmer_status kmer_table_compare(kmer_ctx *a, kmer_ctx *b, uint64_t min_a, uint64_t min_b, kmer_table_overlap *out) {
+    if (!a || !b || !out) return KMER_E_BAD_PARAM;
+    kmer_status st = join_params(a, b);
+    if (st) return st;
+    TabJoin j;
+    bool empty = false;
+    st = join_views(a, b, min_a, min_b, &j, &empty);
+    if (st) return st;
+    uint64_t sums[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!empty) {
+        hipStream_t s = a->stream;
+        uint32_t e = 0, bad[2] = {0, 0};
+        HIPCHK(a, hipMemsetAsync(j.sums, 0, sizeof(sums), s));
+        HIPCHK(a, launch_tab_join_compare(j, s));
+        HIPCHK(a, hipMemcpyAsync(sums, j.sums, sizeof(sums), hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipMemcpyAsync(&e, a->d_err, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipMemcpyAsync(bad, j.badq, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipStreamSynchronize(s));
+        st = join_errors(a, e, bad, "table compare");
+        if (st) return st;
+    }
+    // the record keys of the two contexts, joined by the same rules
+    const auto ra = join_records(a, min_a), rb = join_records(b, min_b);
+    for (auto &kv : ra) {
+        sums[0] += 1;
+        sums[3] += kv.second;
+        const auto it = rb.find(kv.first);
+        if (it == rb.end()) continue;
+        sums[2] += 1;
+        sums[5] += kv.second;
+        sums[6] += it->second;
+        sums[7] += std::min(kv.second, it->second);
+    }
+    for (auto &kv : rb) {
+        sums[1] += 1;
+        sums[4] += kv.second;
+    }
+    out->keys_a = sums[0];
+    out->keys_b = sums[1];
+    out->keys_both = sums[2];
+    out->total_a = sums[3];
+    out->total_b = sums[4];
+    out->shared_a = sums[5];
+    out->shared_b = sums[6];
+    out->sum_min = sums[7];
+    return KMER_OK;
+}
+
+// The device set operation: n keys of k bytes at *keys, their values at
+// *counts, sorted by key bytes, in context a's extract buffers; complete when
+// this returns.  The extract's tail: count, exact allocation, write, sort, decode.
+static kmer_status setop_run(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
+                             const uint8_t **keys, const uint64_t **counts, uint64_t *n_out) {
+    *keys = nullptr;
+    *counts = nullptr;
+    *n_out = 0;
+    TabJoin j;
+    bool empty = false;
+    kmer_status st = join_views(a, b, min_a, min_b, &j, &empty);
+    if (st || empty) return st;
+    hipStream_t s = a->stream;
+    const uint32_t k = a->p.k, cus = (uint32_t)std::max(a->n_cu, 1);
+    const uint32_t walks = op == JOIN_UNION ? 2u : 1u;           // UNION: A's keys, then B's that are not in A
+    j.op = op;
+    uint64_t n = 0;
+    uint32_t e = 0, bad[2] = {0, 0};
+    HIPCHK(a, hipMemsetAsync(j.n_out, 0, 8, s));
+    for (j.second = 0; j.second < walks; ++j.second) HIPCHK(a, launch_tab_join_count(j, s));
+    HIPCHK(a, hipMemcpyAsync(&n, j.n_out, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(&e, a->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(bad, j.badq, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipStreamSynchronize(s));
+    st = join_errors(a, e, bad, "table setop");
+    if (st || !n) return st;
+    size_t tmp_bytes = 0;
+    HIPCHK(a, tab_extract_sort_bytes(n, k, &tmp_bytes));
+    bool ok = a->tmp.ensure(tmp_bytes + 16, s) == hipSuccess && a->tex_keys.ensure(n * k + 4, s) == hipSuccess;
+    for (auto *x : {&a->tex_code, &a->tex_code2, &a->tex_val, &a->tex_val2}) ok = ok && x->ensure(n, s) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(a, KMER_E_OOM, "device allocation failed (" + std::to_string(n) + " keys of a set operation)");
+    }
+    j.cap_out = n;
+    j.codes = a->tex_code.p;
+    j.vals = a->tex_val.p;
+    const uint64_t *sc = nullptr, *sv = nullptr;
+    uint64_t wrote = 0;
+    HIPCHK(a, hipMemsetAsync(j.n_out, 0, 8, s));
+    for (j.second = 0; j.second < walks; ++j.second) HIPCHK(a, launch_tab_join_write(j, s));
+    HIPCHK(a, launch_tab_extract_sort(a->tex_code.p, a->tex_code2.p, a->tex_val.p, a->tex_val2.p, n, k, a->tmp.p,
+                                      tmp_bytes, &sc, &sv, s));
+    HIPCHK(a, launch_tab_extract_decode(sc, n, k, a->tex_keys.p, cus, s));
+    HIPCHK(a, hipMemcpyAsync(&wrote, j.n_out, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(&e, a->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(bad, j.badq, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipStreamSynchronize(s));
+    st = join_errors(a, e, bad, "table setop");
+    if (st) return st;
+    if (wrote != n) return fail(a, KMER_E_DEVICE, "table setop: counted and written keys differ");
+    *keys = a->tex_keys.p;
+    *counts = sv;
+    *n_out = n;
+    return KMER_OK;
+}
+
+kmer_status kmer_table_setop_device(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
+                                    const void **d_keys, const void **d_counts, uint64_t *n) {
+    if (!a || !b || !d_keys || !d_counts || !n || op > KMER_SETOP_UNION) return KMER_E_BAD_PARAM;
+    const kmer_status st = join_params(a, b);
+    if (st) return st;
+    const uint8_t *dk = nullptr;
+    const uint64_t *dc = nullptr;
+    const kmer_status es = setop_run(a, b, op, min_a, min_b, &dk, &dc, n);
+    *d_keys = dk;
+    *d_counts = dc;
+    return es;
+}
+
+kmer_status kmer_table_setop(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b, kmer_result **out) {
+    if (!a || !b || !out || op > KMER_SETOP_UNION) return KMER_E_BAD_PARAM;
+    kmer_status st = join_params(a, b);
+    if (st) return st;
+    const uint8_t *dk = nullptr;
+    const uint64_t *dc = nullptr;
+    uint64_t n = 0;
+    st = setop_run(a, b, op, min_a, min_b, &dk, &dc, &n);
+    if (st) return st;
+    const uint64_t k = a->p.k;
+    std::vector<char> kb(n * k);
+    std::vector<uint64_t> cnt(n);
+    if (n) {
+        hipStream_t s = a->stream;
+        HIPCHK(a, hipMemcpyAsync(kb.data(), dk, n * k, hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipMemcpyAsync(cnt.data(), dc, n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipStreamSynchronize(s));
+    }
+    // the record keys of the two contexts, joined by the same rules
+    const auto ra = join_records(a, min_a), rb = join_records(b, min_b);
+    std::vector<std::pair<std::string, uint64_t>> recs, rows;
+    for (auto &kv : ra) {
+        const auto it = rb.find(kv.first);
+        if (op == KMER_SETOP_INTERSECT) {
+            if (it != rb.end()) recs.emplace_back(kv.first, std::min(kv.second, it->second));
+        } else if (op == KMER_SETOP_SUBTRACT) {
+            if (it == rb.end()) recs.push_back(kv);
+        } else {
+            recs.emplace_back(kv.first, kv.second + (it != rb.end() ? it->second : 0));
+        }
+    }
+    if (op == KMER_SETOP_UNION)
+        for (auto &kv : rb)
+            if (!ra.count(kv.first)) recs.push_back(kv);
+    merge_rows(kb, cnt, k, recs, rows);
+    StreamPos pos;
+    st = read_pos(a, &pos);
+    if (st) return st;
+    kmer_result *r = new (std::nothrow) kmer_result();
+    if (!r) return fail(a, KMER_E_OOM, "host allocation failed");
+    r->lines = a->fasta ? a->fa_lines : pos.lines + pos.ends_open;
     for (auto &e : rows) {
         r->keys.insert(r->keys.end(), e.first.begin(), e.first.end());
         r->offsets.push_back(r->keys.size());

@@ -270,6 +270,7 @@ struct kmer_ctx {
     DBuf<unsigned long long> tab_hist;   // spectrum: AB_HIST_BINS bins, then [0..1] the last bin, [2] extract count / cursor
     DBuf<uint64_t> tex_code, tex_code2, tex_val, tex_val2;   // extract: (2-bit code, value) pairs and the sort's twins
     DBuf<uint8_t> tex_keys;        // extract: the sorted keys' bytes (valid until the next extract)
+    DBuf<unsigned long long> tjoin;   // set operations (kmer_setops.hip): [0..7] compare's sums, [8] setop count / cursor
     uint64_t t_lines = 0;          // a group: the input lines of its last count (kmer_table_extract)
     hipEvent_t tev[8] = {};        // table phase events
     // multi-device group (kmer_params.ndev > 1): one child context per device;

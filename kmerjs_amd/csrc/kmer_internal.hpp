@@ -861,6 +861,76 @@ hipError_t launch_tab_extract_sort(uint64_t *codes, uint64_t *codes2, uint64_t *
                                    const uint64_t **sorted_vals, hipStream_t s);
 hipError_t launch_tab_extract_decode(const uint64_t *codes, uint64_t n, uint32_t k, uint8_t *keys, uint32_t n_cu,
                                      hipStream_t s);
+// Set operations of two finished tables (kmer_setops.hip): bucket q of A can
+// only meet bucket q of B (same k, hash and 2^20 buckets), so the tables are
+// joined bucket by bucket, on the class (the remainder); the Map keys and the
+// doubling of a class (tab_entry_keys) are the same on both sides and are
+// applied afterwards.  A pair of long buckets is joined by one wave in its LDS
+// slice: the staged side S as an open-addressing table of at most JOIN_SLOTS
+// slots keyed by remainder (at most JOIN_TILE entries in join_slots(entries)
+// slots, load <= 1/2; slot value 0 = empty: a staged entry has a count field
+// > 0), the probing side P streamed.
+// A side of more than JOIN_TILE entries is split by leading bits of the
+// remainder's significant part (narrow keys: the low TAB_NSH bits are 0) into
+// ranges (depth s, index t): a range that still holds more than JOIN_TILE
+// entries of S is halved, (s, t) -> (s + 1, 2 t) and (s + 1, 2 t + 1).
+// Remainders within a bucket are distinct, so a range of width 1 holds one
+// entry and the halving ends at s <= join_width.  The helpers below are the
+// whole arithmetic (checked on the CPU by tests/native/setops_keys_check.hip).
+constexpr uint32_t JOIN_TILE = 1024;                   // staged entries per wave (16 KiB of LDS at load 1/2)
+constexpr uint32_t JOIN_SLOTS = 2 * JOIN_TILE;
+constexpr uint32_t JOIN_LANE_MAX = 16;                 // both buckets up to this long: the pair's own lane joins them
+// the significant bits of a remainder and their number
+__host__ __device__ inline uint32_t join_width(bool narrow) { return narrow ? TAB_RBITS - TAB_NSH : TAB_RBITS; }
+__host__ __device__ inline uint64_t join_sig(uint64_t rem, bool narrow) { return narrow ? rem >> TAB_NSH : rem; }
+// the first split depth tried for a staged side of len entries: 0 when it fits
+// the tile, else the depth at which the mean range is at most 3/4 of a tile
+__host__ __device__ inline uint32_t join_depth0(uint64_t len) {
+    uint32_t s = 0;
+    if (len <= JOIN_TILE) return 0;
+    while ((len >> s) > JOIN_TILE * 3 / 4) ++s;
+    return s;
+}
+// the range of depth s (<= width) that holds sig: its leading s bits
+__host__ __device__ inline uint64_t join_sub(uint64_t sig, uint32_t width, uint32_t s) {
+    return s ? sig >> (width - s) : 0;
+}
+// the range after (s, t) is done, ranges above depth s0 in depth-first order;
+// false after the last one
+__host__ __device__ inline bool join_next(uint32_t s0, uint32_t *s, uint64_t *t) {
+    while (*s > s0 && (*t & 1)) {
+        *t >>= 1;
+        --*s;
+    }
+    ++*t;
+    return !(*s == s0 && *t == (1ull << s0));
+}
+// the slots of a table of n <= JOIN_TILE staged entries: a power of two >= 2 n, at least a wave's 64
+__host__ __device__ inline uint32_t join_slots(uint32_t n) {
+    uint32_t m = 64;
+    while (m < 2 * n && m < JOIN_SLOTS) m <<= 1;
+    return m;
+}
+// first slot probed for sig in a table of nslots slots (then linear, wrapping)
+__host__ __device__ inline uint32_t join_slot(uint64_t sig, uint32_t nslots) {
+    return (uint32_t)((sig * TAB_MUL) >> 40) & (nslots - 1);
+}
+enum { JOIN_INTERSECT = 0, JOIN_SUBTRACT = 1, JOIN_UNION = 2 };   // (KMER_SETOP_*)
+struct TabJoin {
+    TabView a, b;                  // nd == nullptr: an empty table; the key parameters (k, prefix, mode) are a's
+    uint64_t min_a, min_b;         // a key is in a side iff its value there is >= this (>= 1)
+    uint32_t op;                   // setop: JOIN_*
+    uint32_t second;               // JOIN_UNION's second walk: B's keys that are not in A
+    unsigned long long *sums;      // compare: the 8 words of kmer_table_overlap
+    unsigned long long *n_out;     // setop: counted keys, then the write cursor
+    uint64_t cap_out;
+    uint64_t *codes, *vals;        // setop: (2-bit code, value) pairs, as the extract's
+    unsigned int *err;             // ERR_TAB_LOOKUP / ERR_TAB_EXTRACT ...
+    uint32_t *badq;                // ... [0] the bucket, [1] the side (0 a, 1 b)
+};
+hipError_t launch_tab_join_compare(const TabJoin &j, hipStream_t s);
+hipError_t launch_tab_join_count(const TabJoin &j, hipStream_t s);
+hipError_t launch_tab_join_write(const TabJoin &j, hipStream_t s);
 // multi-GPU table exchange: copy n segments {src offset, dst offset, length}
 // of u64 keys (one workgroup per segment, grid-strided)
 struct TabSeg {

@@ -343,7 +343,8 @@ class KmerFinder:
             if own:
                 match.close()
 
-    def find_matches_table(self, counter, query_size=None, with_removed=False, min_count=1):
+    def find_matches_table(self, counter, query_size=None, with_removed=False, min_count=1, exclude=None,
+                           exclude_min=1):
         """findMatches with a table-mode count as the query (a Counter opened
         with FLAG_UNORDERED / FLAG_CANONICAL, after its finish): the join runs
         on the device against the counter's table.  query_size defaults to the
@@ -353,7 +354,16 @@ class KmerFinder:
         min_count > 1: the query is the Map's keys of value >= min_count (the
         reference's `v >= coverage`, lib/index.js:190), extracted on the device
         (Counter.table_extract_device) and joined as a device result;
-        query_size then defaults to their number."""
+        query_size then defaults to their number.
+        exclude (another table-mode Counter with the same k, mode and prefix,
+        e.g. a host or contaminant sample): its keys of value >= exclude_min
+        are taken out of the query first -- SUBTRACT(counter, exclude,
+        min_count, exclude_min) on the device (Counter.table_setop_device),
+        joined as a device result like the min_count route."""
+        if exclude is not None:
+            from ._native import SETOP_SUBTRACT
+            res = counter.table_setop_device(exclude, SETOP_SUBTRACT, min_count, exclude_min)
+            return self._find_matches_device(counter, res, query_size, with_removed)
         if min_count > 1:
             return self._find_matches_extract(counter, query_size, with_removed, min_count)
         if query_size is None:
@@ -369,7 +379,11 @@ class KmerFinder:
             m.close()
 
     def _find_matches_extract(self, counter, query_size, with_removed, min_count):
-        d_keys, d_counts, n = counter.table_extract_device(min_count)
+        return self._find_matches_device(counter, counter.table_extract_device(min_count), query_size, with_removed)
+
+    def _find_matches_device(self, counter, res, query_size, with_removed):
+        """findMatches over (d_keys, d_counts, n): sorted keys of the counter's k in device memory."""
+        d_keys, d_counts, n = res
         if query_size is None:
             query_size = n
         m = Match(self.db, device_result=(d_keys, counter.k, d_counts, n))
