@@ -174,6 +174,7 @@ kmer_status kmer_open(const kmer_params *pp, kmer_ctx **out) {
     if (ok) {
         ok &= hipMemset(c->d_scal, 0, 128) == hipSuccess;
         c->d_hticket = (unsigned int *)(c->d_scal + 8);
+        c->d_cross_go = (unsigned int *)(c->d_scal + 9);
         c->d_rec_count = (unsigned long long *)(c->d_scal + 0);
         c->d_ovf_count = (unsigned long long *)(c->d_scal + 1);
         c->d_xcount = (unsigned long long *)(c->d_scal + 2);

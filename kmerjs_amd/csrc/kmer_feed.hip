@@ -194,8 +194,9 @@ void bind_hits(kmer_ctx *c, HitArgs &h) {
     h.rcap = rcap;
 }
 
-// One attempt at the pending chunk: scan, tile scan, hit resolution and the
-// chunk tail (position, counters -> mapped host memory), all on the stream.
+// One attempt at the pending chunk: scan, tile scan, hit resolution, the
+// chunk tail (position, counters -> mapped host memory) and the placement of
+// the chunk's cross hits, all on the stream.
 kmer_status launch_chunk(kmer_ctx *c) {
     auto &p = c->pend;
     const hipStream_t s = p.s;
@@ -217,6 +218,12 @@ kmer_status launch_chunk(kmer_ctx *c) {
     p.h.seq = ++c->tail_seq;
     p.h.stamp = stamp;
     HIPCHK(c, launch_hits(p.h, s));          // (+ the chunk tail: position, counters, stamps -> h_tail)
+    // A sequence line lies inside one chunk, so the chunk's cross hits are
+    // placed now, sized on the device, while the host wakes up on the tail
+    // (wide keys need cross_wide_fix: at the finish)
+    if (c->mode == MODE_PACKED && !c->wide)
+        HIPCHK(c, launch_cross_segsort_chunk(p.h.xord, p.h.xkey, p.h.xslot, p.h.xbase, p.h.xcap, c->d_xcount,
+                                             c->d_cross_go, p.h.rkey, p.h.rkey32, p.h.rord, c->pbits, s));
     if (s != c->stream) {                        // later work follows the chunk
         HIPCHK(c, hipEventRecord(c->evw, s));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
@@ -296,6 +303,7 @@ kmer_status scan_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_ti
     h.ticket = c->d_hticket;
     h.chunk_hits = c->d_chunk_hits;
     h.chunk_cross = c->d_xcount;
+    h.cross_go = c->d_cross_go;
     h.ends_open = c->d_ends_open;
     h.host_out = c->d_tail;
     p.init.cnt = 0;
@@ -374,7 +382,8 @@ kmer_status settle(kmer_ctx *c) {
     }
     if (packed) {
         c->n_hits += c->h_small[3];
-        c->n_cross += c->h_small[2];
+        // (without CROSS_HOST_BITS the device has placed the chunk's cross hits: launch_chunk)
+        if (c->wide || ((uint32_t)c->h_small[5] & CROSS_HOST_BITS)) c->n_cross += c->h_small[2];
         c->long_seg |= (c->h_small[5] & INFO_LONGSEG) != 0;
     }
     c->chunk_open = c->h_small[7] != 0;

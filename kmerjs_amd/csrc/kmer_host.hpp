@@ -222,6 +222,7 @@ struct kmer_ctx {
     std::vector<hipStream_t> up_streams;
     uint64_t *d_tail = nullptr;    // ... its device address
     unsigned int *d_hticket = nullptr;   // chunk tail last-block ticket (d_scal[8])
+    unsigned int *d_cross_go = nullptr;  // chunk tail: the device places the chunk's cross hits (d_scal[9])
     uint64_t tail_seq = 0;         // last chunk sequence number handed to the chunk tail kernel
     uint32_t prep_flags = 0;       // PREP_RESET / PREP_SETPOS pending for the next feed's prologue
     // the last packed-path chunk, launched but not yet settled (its tail read,

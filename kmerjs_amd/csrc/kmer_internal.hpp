@@ -53,6 +53,11 @@ enum : uint32_t {
     // slots -- cross segments may be long (finish sorts the whole cross list)
     INFO_LONGSEG = 1u << 16,
 };
+// With any of these in the error word at the chunk tail a chunk's cross
+// entries wait for the host (finish sorts the whole list, or the chunk is
+// redone); without, the device places them right behind the chunk
+// (cross_segsort_chunk_kernel).
+constexpr uint32_t CROSS_HOST_BITS = INFO_LONGSEG | ERR_OVF_OVERFLOW | ERR_REC_OVERFLOW | ERR_CROSS_OVERFLOW;
 
 // look-back word: [63:62] status, [61:0] value
 constexpr uint64_t LB_AGG = 1ull << 62;
@@ -194,6 +199,7 @@ struct HitArgs {
     uint64_t *scal;                // device scalars [0..7] (see kmer_ctx::d_scal)
     unsigned int *ticket;          // last-block ticket (returned to 0 by the last block)
     unsigned long long *chunk_hits, *chunk_cross, *ends_open;
+    unsigned int *cross_go;        // 1: the error word at the tail has none of CROSS_HOST_BITS
     uint64_t *host_out;            // mapped host memory: copy of scal[0..7], then [9] = seq
     uint64_t seq;                  // chunk sequence number (the host waits for it in host_out[9])
     uint64_t *stamp;               // device clock stamps (STAMP_*): the tail writes FEED_END and copies
@@ -396,6 +402,10 @@ hipError_t launch_cross_sort_small(const uint32_t *slot, const uint64_t *ord, co
 constexpr uint64_t XSMALL_MAX = 16384;   // cross lists up to this size: one-workgroup sort
 hipError_t launch_cross_segsort(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t n, uint64_t *rkey,
                                 uint32_t *rkey32, uint64_t *rord, uint32_t pbits, uint64_t *stamp, hipStream_t s);
+// the chunk's cross entries [xbase, xbase + *count), placed on the device if the chunk tail set *go
+hipError_t launch_cross_segsort_chunk(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t xbase, uint64_t xcap,
+                                      const unsigned long long *count, const unsigned int *go, uint64_t *rkey,
+                                      uint32_t *rkey32, uint64_t *rord, uint32_t pbits, hipStream_t s);
 hipError_t launch_heads(const uint64_t *skey, const uint32_t *srank, uint64_t n, uint64_t invalid_key,
                         const uint64_t *rcnt, HeadRec *hrec, uint32_t *hcnt, hipStream_t s);
 // sort finish without per-entry counts: hcnt prefilled with 1, only groups of >= 2 and invalid keys written

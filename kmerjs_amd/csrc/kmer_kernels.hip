@@ -647,6 +647,11 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
     const uint32_t tile = blockIdx.x;
     const int64_t g0 = (int64_t)tile * TILE;
     {
+        // (the prefix byte is loaded in front of the tile's loads, in flight
+        // with them: behind them it was one more dependent round trip for
+        // waves 0 and 1 in front of the first barrier)
+        uint8_t prb = 0;
+        if (tid < 2 * KMAX_TILE) prb = a.PR[tid];
         TileRegs r;
         load_tile(a.data, len, g0, r);
         if (tid == 0) {
@@ -656,7 +661,7 @@ __global__ __launch_bounds__(TPB) void scan_tile_kernel(ScanArgs a) {
             sh.qn = 0;
         }
         const uint32_t orall = store_tile(r, buf);
-        if (tid < 2 * KMAX_TILE) s_pr[tid] = a.PR[tid];     // (behind the tile loads)
+        if (tid < 2 * KMAX_TILE) s_pr[tid] = prb;
         if (orall & 0x80808080u) atomicOr(a.err, ERR_NONASCII);
     }
     __syncthreads();
@@ -844,6 +849,12 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     const uint32_t tile = blockIdx.x;
     const int64_t g0 = (int64_t)tile * TILE;
     {
+        // The prefix bytes are read only where the lengths are run-time values
+        // (emit_hit: prefix bytes past the fifth); there the byte is loaded in
+        // front of the tile's loads, in flight with them, not behind them as
+        // one more dependent round trip in front of the first barrier.
+        uint8_t prb = 0;
+        if (K == 0 && tid < 2 * KMAX_TILE) prb = a.PR[tid];
         TileRegs r;
         load_tile(a.data, len, g0, r);
         if (tid == 0) {
@@ -853,7 +864,7 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
             sh.qn = 0;
         }
         const uint32_t orall = store_tile(r, buf);
-        if (tid < 2 * KMAX_TILE) s_pr[tid] = a.PR[tid];
+        if (K == 0 && tid < 2 * KMAX_TILE) s_pr[tid] = prb;
         if (orall & 0x80808080u) atomicOr(a.err, ERR_NONASCII);
     }
     __syncthreads();
@@ -1280,10 +1291,14 @@ __global__ __launch_bounds__(256) void hit_overflow_kernel(HitArgs a) {
     *a.chunk_cross = a.tscan[nt - 1].nx + a.tsum[nt - 1].nx;
     *a.ticket = 0;
     if (a.stamp) a.stamp[STAMP_FEED_END] = wall_clock64();
+    // whether cross_segsort_chunk_kernel places the chunk's cross hits: decided
+    // here, on the error word that the host gets, so that both act on one value
+    const uint64_t errw = __hip_atomic_load(a.scal + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *a.cross_go = ((uint32_t)errw & CROSS_HOST_BITS) ? 0u : 1u;
     __threadfence();
     if (a.host_out) {
         for (int i = 0; i < 8; ++i)
-            a.host_out[i] = __hip_atomic_load(a.scal + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.host_out[i] = i == 5 ? errw : __hip_atomic_load(a.scal + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (a.stamp)                             // (scan start, scan end, feed end: the chunk's phase times)
             for (int i = 0; i <= (int)STAMP_FEED_END; ++i)
                 a.host_out[TAIL_STAMP + i] = __hip_atomic_load(a.stamp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2451,15 +2466,15 @@ __global__ __launch_bounds__(1024) void cross_sort_small_kernel(const uint32_t *
 // ordered by line, and one line's entries come from at most two tiles
 // (<= 2 * HMAX).  One thread per line segment: insertion sort by order key,
 // then the scatter to the natural slots.
-__global__ __launch_bounds__(256) void cross_segsort_kernel(uint64_t *ord, uint64_t *key, const uint32_t *slot,
-                                                            uint64_t n, uint64_t *rkey, uint32_t *rkey32,
-                                                            uint64_t *rord, uint32_t lsh, uint64_t *stamp) {
-    stamp_now(stamp, STAMP_FINISH_START);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void cross_segsort_range(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t lo,
+                                                    uint64_t hi, uint64_t *rkey, uint32_t *rkey32, uint64_t *rord,
+                                                    uint32_t lsh) {
+    for (uint64_t i = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi;
+         i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t line = ord[i] >> lsh;     // (the line bits of a segment never change while it is sorted)
-        if (i > 0 && (ord[i - 1] >> lsh) == line) continue;
+        if (i > lo && (ord[i - 1] >> lsh) == line) continue;
         uint64_t e = i + 1;
-        while (e < n && (ord[e] >> lsh) == line) ++e;
+        while (e < hi && (ord[e] >> lsh) == line) ++e;
         for (uint64_t j = i + 1; j < e; ++j) {
             const uint64_t v = ord[j], kv = key[j];
             uint64_t p = j;
@@ -2477,6 +2492,27 @@ __global__ __launch_bounds__(256) void cross_segsort_kernel(uint64_t *ord, uint6
             rord[sl] = ord[j];
         }
     }
+}
+__global__ __launch_bounds__(256) void cross_segsort_kernel(uint64_t *ord, uint64_t *key, const uint32_t *slot,
+                                                            uint64_t n, uint64_t *rkey, uint32_t *rkey32,
+                                                            uint64_t *rord, uint32_t lsh, uint64_t *stamp) {
+    stamp_now(stamp, STAMP_FINISH_START);
+    cross_segsort_range(ord, key, slot, 0, n, rkey, rkey32, rord, lsh);
+}
+// Right behind the chunk's hit kernels: the chunk's own cross entries [xbase,
+// xbase + *count) -- a sequence line lies inside one chunk, so they can be
+// placed without the host -- unless the chunk tail found that the host has to
+// look first (CROSS_HOST_BITS in the error word: a long segment, or an
+// overflow after which the chunk is redone).  settle() gets the same error
+// word from the tail and then leaves these entries out of n_cross.
+__global__ __launch_bounds__(256) void cross_segsort_chunk_kernel(uint64_t *ord, uint64_t *key, const uint32_t *slot,
+                                                                  uint64_t xbase, uint64_t xcap,
+                                                                  const unsigned long long *count,
+                                                                  const unsigned int *go, uint64_t *rkey,
+                                                                  uint32_t *rkey32, uint64_t *rord, uint32_t lsh) {
+    if (!*go) return;
+    const uint64_t hi = min(xbase + (uint64_t)*count, xcap);
+    cross_segsort_range(ord, key, slot, xbase, hi, rkey, rkey32, rord, lsh);
 }
 
 // End of the key group starting at sorted index i: galloping then binary search.
@@ -3499,6 +3535,14 @@ hipError_t launch_cross_sort_small(const uint32_t *slot, const uint64_t *ord, co
     if (n > XSMALL) return hipErrorInvalidValue;
     if (n) hipLaunchKernelGGL(cross_sort_small_kernel, dim3(1), dim3(1024), 0, s, slot, ord, key, (uint32_t)n, rkey,
                               rkey32, rord);
+    return hipGetLastError();
+}
+hipError_t launch_cross_segsort_chunk(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t xbase, uint64_t xcap,
+                                      const unsigned long long *count, const unsigned int *go, uint64_t *rkey,
+                                      uint32_t *rkey32, uint64_t *rord, uint32_t pbits, hipStream_t s) {
+    // (a fixed grid: the count is on the device; C2 has ~12 K entries per chunk)
+    hipLaunchKernelGGL(cross_segsort_chunk_kernel, dim3(256), dim3(256), 0, s, ord, key, slot, xbase, xcap, count, go,
+                       rkey, rkey32, rord, pbits + 1);
     return hipGetLastError();
 }
 hipError_t launch_cross_segsort(uint64_t *ord, uint64_t *key, const uint32_t *slot, uint64_t n, uint64_t *rkey,
