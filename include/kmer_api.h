@@ -285,6 +285,70 @@ kmer_status kmer_table_stats(kmer_ctx *ctx, uint64_t *canonical, uint64_t *keys,
  * pointers with n > 0; n == 0 is KMER_OK and touches nothing. */
 kmer_status kmer_table_lookup(kmer_ctx *ctx, const char *keys, uint64_t n, uint64_t *counts);
 kmer_status kmer_table_lookup_device(kmer_ctx *ctx, const void *d_keys, uint64_t n, void *d_counts, void *stream);
+/* Reads screened against the table (after a table finish, until the next
+ * reset; the calls may be repeated and interleaved with stats, digest, lookup,
+ * spectrum, extract, setops and match, and leave the table, its bucket index,
+ * the big list, kmer_lines, the context's records and the session's position
+ * unchanged).  Input is FASTQ bytes: lines are '\n'-separated, line i runs up
+ * to the (i+1)-th '\n' or to the end of the bytes, and the reads are the lines
+ * with i % 4 == 1 and i <= the number of '\n' (data.split("\n")[1::4]); the
+ * line finder works from line phase 0 in every call.  Read r gets one row, in
+ * input order.  "T" is the Map this context's host result describes, the one
+ * kmer_table_lookup answers for; the read's own Map is the one the same
+ * configuration (k, prefix, mode) builds from a file holding that record alone:
+ *   windows = the sum of the own Map's values over its A/C/G/T keys,
+ *   hits    = that sum restricted to keys x with T(x) >= max(min_count, 1),
+ *   sum     = the sum of own(x) * T(x), mod 2^64, over the same keys,
+ *   skipped = the read's forward windows that hold a byte outside A/C/G/T
+ *             (record keys, which live on the host and are not matched).
+ * A line of 0 or 1 bytes gives a zero row (the count ignores it,
+ * lib/kmers.js:151).  Per forward window w of a counted line, with C the
+ * table's count of its class {w, rc w} (0 when absent; a 0xFFFFF count field
+ * resolves through the big list): table mode -- f = "w starts with the
+ * prefix", r = "rc w starts with it"; w != rc w: weight m = f + r, value v = C;
+ * w == rc w: m = 2 f, v = 2 C.  Canonical mode -- m = "the smaller string of
+ * the class starts with the prefix", v = C.  Then windows += m and, if v >=
+ * max(min_count, 1), hits += m and sum += m v.  One probe per forward window,
+ * by class.  An exchanged table answers 0 for classes other ranks own: hits
+ * and sum add up over ranks, windows and skipped are equal on every rank.
+ *
+ * kmer_table_screen_device: the bytes are in device memory, start at a record
+ * start, may end without '\n' and may sit at any byte alignment; nothing
+ * outside [d_bytes, d_bytes + len) is loaded.  The call waits for the work
+ * queued so far on `stream` (as the lookup does); *d_rows = *n_reads rows of
+ * kmer_read_screen, library-owned device memory, complete when the call
+ * returns and valid until the next screen, reset or close (not the extract's
+ * buffers, which stay valid).  A chunk in flight is settled first.
+ * kmer_table_screen: host bytes; they go up in bounded pieces cut at record
+ * boundaries (batch_bytes, default 64 MiB), so device and pinned memory do not
+ * grow with len.  At most cap rows are written; *n_reads is always the true
+ * number, and cap < *n_reads is KMER_E_BAD_PARAM with *n_reads set.
+ *
+ * flags (of the call; kmer_open's flags are not involved): 0 = auto -- the
+ * sorted route when the table's entries divided by the buckets it owns exceed
+ * KMER_SCREEN_DIRECT_MAX, else the direct one.  KMER_SCREEN_DIRECT: windows
+ * are probed in input order, a bucket is scanned per window.
+ * KMER_SCREEN_SORTED: the windows of a piece are sorted by bucket first, and a
+ * long bucket is read once per run of windows.  Both, or an unknown bit:
+ * KMER_E_BAD_PARAM.  KMER_SCREEN_PIECE_TEST (debug): internal pieces of 4,096
+ * windows instead of 2^26, so lines are cut across pieces.
+ *
+ * Checked before any device call: KMER_E_BAD_PARAM for a NULL context or
+ * out-pointer, NULL bytes with len > 0, or bad flags; len == 0 is KMER_OK with
+ * *n_reads = 0 and touches nothing; KMER_E_STATE for a group context (ndev >
+ * 1), a context not in table mode or without a table finish, or a
+ * KMER_FLAG_FASTA context.  KMER_E_NONASCII as for a feed (the table stays
+ * readable); KMER_E_OOM leaves the context usable; KMER_E_DEVICE, naming the
+ * bucket, if a bucket's extent lies past the table (it is not read). */
+typedef struct {
+    uint64_t windows, hits, skipped, sum;
+} kmer_read_screen;
+enum { KMER_SCREEN_DIRECT = 1u, KMER_SCREEN_SORTED = 2u, KMER_SCREEN_PIECE_TEST = 4u };
+#define KMER_SCREEN_DIRECT_MAX 16u /* mean entries per owned bucket up to which auto picks DIRECT */
+kmer_status kmer_table_screen_device(kmer_ctx *ctx, const void *d_bytes, size_t len, uint64_t min_count,
+                                     uint32_t flags, void *stream, const void **d_rows, uint64_t *n_reads);
+kmer_status kmer_table_screen(kmer_ctx *ctx, const uint8_t *bytes, size_t len, uint64_t min_count,
+                              uint32_t flags, kmer_read_screen *rows, uint64_t cap, uint64_t *n_reads);
 /* The table read by value (after a table finish, until the next reset; the
  * calls may be repeated and interleaved with stats, digest, lookup and match,
  * and leave the table unchanged).  "The Map" is the Map this context's host

@@ -35,6 +35,12 @@ SETOP_INTERSECT = 0
 SETOP_SUBTRACT = 1
 SETOP_UNION = 2
 JOIN_TILE = 1024
+# kmer_table_screen* (include/kmer_api.h, KMER_SCREEN_*): the route bits of a call (0: auto), the
+# debug bit for 4,096-window pieces, and the mean entries per owned bucket up to which auto is direct
+SCREEN_DIRECT = 1
+SCREEN_SORTED = 2
+SCREEN_PIECE_TEST = 4
+SCREEN_DIRECT_MAX = 16
 WRITE_JSON = 0      # JSON.stringify(mapToJSON(map)), lib/kmers.js:46-54
 WRITE_LEGACY = 1    # "{\nkey: count,...}\n", lib/index.js:381-388
 
@@ -49,6 +55,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_last_timing", "kmer_phase_times", "kmer_table_stats", "kmer_table_digest", "kmer_table_routes", "kmer_table_device",
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
            "kmer_table_lookup", "kmer_table_lookup_device",
+           "kmer_table_screen_device", "kmer_table_screen",
            "kmer_table_spectrum", "kmer_table_extract_device", "kmer_table_extract",
            "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
@@ -72,6 +79,11 @@ class TableOverlap(ctypes.Structure):
     """kmer_table_overlap (kmer_table_compare)."""
     _fields_ = [(name, ctypes.c_uint64) for name in ("keys_a", "keys_b", "keys_both", "total_a", "total_b",
                                                       "shared_a", "shared_b", "sum_min")]
+
+
+class ReadScreen(ctypes.Structure):
+    """kmer_read_screen (kmer_table_screen): one row per read."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("windows", "hits", "skipped", "sum")]
 
 
 class Params(ctypes.Structure):
@@ -150,6 +162,10 @@ def _load():
         "kmer_table_finish_exchanged": (ctypes.c_int, [vp, vp, u64, pu64, ctypes.c_uint32, ctypes.c_uint32, vp]),
         "kmer_table_lookup": (ctypes.c_int, [vp, ctypes.c_char_p, u64, pu64]),
         "kmer_table_lookup_device": (ctypes.c_int, [vp, vp, u64, vp, vp]),
+        "kmer_table_screen_device": (ctypes.c_int, [vp, vp, ctypes.c_size_t, u64, ctypes.c_uint32, vp,
+                                                    ctypes.POINTER(vp), pu64]),
+        "kmer_table_screen": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, u64, ctypes.c_uint32,
+                                             ctypes.POINTER(ReadScreen), u64, pu64]),
         "kmer_table_spectrum": (ctypes.c_int, [vp, ctypes.c_uint32, pu64, pu64]),
         "kmer_table_extract_device": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp), ctypes.POINTER(vp), pu64]),
         "kmer_table_extract": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp)]),
@@ -456,6 +472,34 @@ class Counter:
         ordered after the work queued on `stream`, complete on return."""
         self._check(LIB.kmer_table_lookup_device(self.h, ctypes.c_void_p(d_keys), n, ctypes.c_void_p(d_counts),
                                                  ctypes.c_void_p(stream)), "table_lookup_device")
+
+    def table_screen_device(self, ptr: int, nbytes: int, min_count=1, flags=0, stream: int = 0):
+        """kmer_table_screen_device: FASTQ bytes in device memory (from a record
+        start, any alignment) screened against the table -> (d_rows, n): n rows
+        of four uint64 {windows, hits, skipped, sum}, one per read in input
+        order, in device memory the library owns -- complete on return, valid
+        until the next screen, reset or close.  flags: 0 (auto), SCREEN_DIRECT
+        or SCREEN_SORTED, | SCREEN_PIECE_TEST."""
+        rows, n = ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(LIB.kmer_table_screen_device(self.h, ctypes.c_void_p(ptr), nbytes, min_count, flags,
+                                                 ctypes.c_void_p(stream), ctypes.byref(rows), ctypes.byref(n)),
+                    "table_screen_device")
+        return rows.value or 0, n.value
+
+    def table_screen(self, data: bytes, min_count=1, flags=0):
+        """kmer_table_screen: FASTQ bytes on the host -> an (n, 4) numpy uint64
+        array, one row per read (data.split(b"\n")[1::4]) in input order;
+        columns: windows, hits, skipped, sum."""
+        import numpy as np
+        data = bytes(data)
+        nl = data.count(b"\n")
+        cap = (nl - 1) // 4 + 1 if nl else 0
+        out = np.zeros((cap, 4), dtype=np.uint64)
+        n = ctypes.c_uint64()
+        self._check(LIB.kmer_table_screen(self.h, data, len(data), min_count, flags,
+                                          out.ctypes.data_as(ctypes.POINTER(ReadScreen)), cap, ctypes.byref(n)),
+                    "table_screen")
+        return out[:n.value]
 
     def table_spectrum(self, nbins=256):
         """Table mode, after a finish: the abundance spectrum of the Map --

@@ -287,6 +287,11 @@ kmer_status kmer_close(kmer_ctx *c) {
     for (auto *b : {&c->tex_code, &c->tex_code2, &c->tex_val, &c->tex_val2}) b->release();
     c->tex_keys.release();
     c->tjoin.release();
+    for (auto *b : {&c->tsc_h, &c->tsc_val}) b->release();
+    for (auto *b : {&c->tsc_bkt, &c->tsc_bkt2, &c->tsc_idx, &c->tsc_idx2}) b->release();
+    c->tsc_code.release();
+    c->tsc_rows.release();
+    c->tsc_in.release();
     c->gm_keys.release();
     c->gm_keys2.release();
     for (auto *b : {&c->gm_cnt, &c->gm_cnt2, &c->gm_first, &c->gm_first2, &c->gm_h1, &c->gm_h2, &c->gm_h1b, &c->gm_h2b})
@@ -814,6 +819,18 @@ static kmer_status lookup_state(kmer_ctx *c) {
 // The finished table (not empty) as its readers see it: the one place that
 // names the context's table buffers (the lookup below; the matcher's probe
 // through table_view)
+static void view_key_params(const kmer_ctx *c, TabView *v) {
+    v->k = c->p.k;
+    v->plo = v->phi = 0;
+    for (size_t i = 0; i < c->prefix.size(); ++i) {
+        const uint8_t ch = (uint8_t)c->prefix[i];
+        v->plo |= ((((uint32_t)ch >> 1) ^ ((uint32_t)ch >> 2)) & 1u) << i;
+        v->phi |= (((uint32_t)ch >> 2) & 1u) << i;
+    }
+    v->pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
+    v->canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
+}
+
 static kmer_status fill_view(kmer_ctx *c, TabView *v) {
     if (!c->t_ent || !c->tstart.p || !c->tnd.p || !c->tbig.p) return fail(c, KMER_E_STATE, "no table finish yet");
     HIPCHK(c, c->tlk_bad.ensure(1, c->stream));
@@ -824,14 +841,7 @@ static kmer_status fill_view(kmer_ctx *c, TabView *v) {
     v->cap = c->t_keys;
     v->big = c->tbig.p;
     v->n_big = std::min<uint64_t>(c->t_nbig, c->tbig.cap);
-    v->k = c->p.k;
-    for (size_t i = 0; i < c->prefix.size(); ++i) {
-        const uint8_t ch = (uint8_t)c->prefix[i];
-        v->plo |= ((((uint32_t)ch >> 1) ^ ((uint32_t)ch >> 2)) & 1u) << i;
-        v->phi |= (((uint32_t)ch >> 2) & 1u) << i;
-    }
-    v->pmask = c->prefix.size() >= 32 ? ~0u : ((1u << c->prefix.size()) - 1u);
-    v->canonical = (c->p.flags & KMER_FLAG_CANONICAL) ? 1u : 0u;
+    view_key_params(c, v);
     v->err = c->d_err;
     v->badq = c->tlk_bad.p;
     return KMER_OK;
@@ -932,6 +942,200 @@ kmer_status kmer_table_lookup_device(kmer_ctx *c, const void *d_keys, uint64_t n
     HIPCHK(c, hipEventRecord(c->evw, (hipStream_t)stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
     return lookup_run(c, (const uint8_t *)d_keys, n, (uint64_t *)d_counts);
+}
+
+// ---- read screen (kmer_screen.hip) ----
+static_assert(sizeof(kmer_read_screen) == sizeof(ScreenRow) && sizeof(ScreenRow) == 32,
+              "kmer_read_screen: the reduce kernel's row");
+constexpr uint64_t SCREEN_BATCH = 64ull << 20;   // bytes per upload of the host call (batch_bytes overrides)
+
+static bool screen_bad_flags(uint32_t flags) {
+    const uint32_t all = KMER_SCREEN_DIRECT | KMER_SCREEN_SORTED | KMER_SCREEN_PIECE_TEST;
+    return (flags & ~all) || ((flags & KMER_SCREEN_DIRECT) && (flags & KMER_SCREEN_SORTED));
+}
+
+// the state a screen needs, checked before any device call
+static kmer_status screen_state(kmer_ctx *c) {
+    if (!c->group.empty()) return fail(c, KMER_E_STATE, "single-device call on a group context");
+    if (c->mode != MODE_TABLE) return fail(c, KMER_E_STATE, "not a table-mode context (KMER_FLAG_UNORDERED)");
+    if (c->fasta) return fail(c, KMER_E_STATE, "read screen: FASTQ input only (the context has KMER_FLAG_FASTA)");
+    const kmer_status st = settle(c);
+    if (st) return st;
+    if (!c->t_done) return fail(c, KMER_E_STATE, "no table finish yet");
+    return KMER_OK;
+}
+
+// The screen of len device-resident bytes that start at a record start, queued
+// on the context's stream and waited for: c->tsc_rows holds *n_reads rows.
+static kmer_status screen_run(kmer_ctx *c, const uint8_t *d, uint64_t len, uint64_t min_count, uint32_t flags,
+                              uint64_t *n_reads) {
+    hipStream_t s = c->stream;
+    *n_reads = 0;
+    const uint64_t n_tiles64 = (len + TILE - 1) / TILE;
+    if (n_tiles64 > 0x7FFFFFFFull) return fail(c, KMER_E_BAD_PARAM, "read screen: input too large for one call");
+    const uint32_t n_tiles = (uint32_t)n_tiles64;
+    if (!screen_ensure(c->tcount, n_tiles, s) || !screen_ensure(c->tbase, n_tiles, s) ||
+        !screen_ensure(c->nlslots, (uint64_t)n_tiles * NL_SLOTS, s))
+        return fail(c, KMER_E_OOM, "device allocation failed (read screen: line finder)");
+    // the line finder from line phase 0, whatever the session's position is
+    const uint64_t saved_lines = c->host_lines;
+    c->host_lines = 0;
+    uint64_t n_nl = 0, n_seq = 0;
+    kmer_status st = chunk_lines(c, d, len, n_tiles, s, false, &n_nl, &n_seq);
+    c->host_lines = saved_lines;
+    if (st == KMER_E_NONASCII) {                     // (reported, not kept: the table stays readable)
+        const std::string msg = c->err;
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)((uint32_t)c->h_small[5] & ~ERR_NONASCII), 1, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, st, msg);
+    }
+    if (st) return st;
+    *n_reads = n_seq;
+    if (!n_seq) return KMER_OK;
+    if (!screen_ensure(c->tsc_rows, n_seq, s) || !screen_ensure(c->wbase, n_seq, s))
+        return fail(c, KMER_E_OOM, "device allocation failed (" + std::to_string(n_seq) + " screened reads)");
+    HIPCHK(c, hipMemsetAsync(c->tsc_rows.p, 0, n_seq * sizeof(ScreenRow), s));
+    ROCPRIM_RUN(c, rocprim::exclusive_scan(t, b, c->wcount.p, c->wbase.p, (uint64_t)0, (size_t)n_seq,
+                                           rocprim::plus<uint64_t>(), s));
+    HIPCHK(c, hipMemcpyAsync(c->h_small + 14, c->wbase.p + n_seq - 1, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_small + 15, c->wcount.p + n_seq - 1, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint64_t total = (c->h_small[14] + c->h_small[15]) / 2;   // (wcount: both strands' windows)
+    if (!total) return KMER_OK;
+    const bool table = c->t_keys != 0;               // (an empty table: every value is 0)
+    const bool sorted = table && ((flags & KMER_SCREEN_SORTED) ||
+                                  (!(flags & KMER_SCREEN_DIRECT) &&
+                                   c->t_canon > (uint64_t)KMER_SCREEN_DIRECT_MAX * std::max(c->t_nq, 1u)));
+    const uint64_t piece = (flags & KMER_SCREEN_PIECE_TEST) ? SC_PIECE_TEST : SC_PIECE;
+    const uint64_t cap = std::min(total, piece);
+    size_t tmp_bytes = 0;
+    bool ok = screen_ensure(c->tsc_h, cap, s) && screen_ensure(c->tsc_val, cap, s) && screen_ensure(c->tsc_code, cap, s);
+    if (ok && sorted) {
+        HIPCHK(c, screen_sort_bytes(cap, &tmp_bytes));
+        for (auto *b : {&c->tsc_bkt, &c->tsc_bkt2, &c->tsc_idx, &c->tsc_idx2}) ok = ok && screen_ensure(*b, cap, s);
+        ok = ok && screen_ensure(c->tmp, tmp_bytes + 16, s);
+    }
+    if (!ok) return fail(c, KMER_E_OOM, "device allocation failed (read screen: " + std::to_string(cap) + " windows)");
+    TabScreen a;
+    memset(&a, 0, sizeof(a));
+    if (table) {
+        st = fill_view(c, &a);
+        if (st) return st;
+    } else {
+        view_key_params(c, &a);
+    }
+    const uint32_t cus = (uint32_t)std::max(c->n_cu, 1);
+    a.data = d;
+    a.len = len;
+    a.lines = c->lines.p;
+    a.wbase2 = c->wbase.p;
+    a.n_reads = n_seq;
+    a.total = total;
+    a.h = c->tsc_h.p;
+    a.code = c->tsc_code.p;
+    a.val = c->tsc_val.p;
+    a.bkt = sorted ? c->tsc_bkt.p : nullptr;
+    a.idx = sorted ? c->tsc_idx.p : nullptr;
+    a.min_count = std::max<uint64_t>(min_count, 1);
+    a.rows = c->tsc_rows.p;
+    for (uint64_t p0 = 0; p0 < total; p0 += piece) {
+        a.p0 = p0;
+        a.m = std::min(piece, total - p0);
+        HIPCHK(c, launch_screen_keys(a, cus, s));
+        if (!table) {
+            HIPCHK(c, hipMemsetAsync(a.val, 0, a.m * 8, s));
+        } else if (sorted) {
+            const uint32_t *sb = nullptr, *si = nullptr;
+            HIPCHK(c, launch_screen_sort(c->tsc_bkt.p, c->tsc_bkt2.p, c->tsc_idx.p, c->tsc_idx2.p, a.m, c->tmp.p,
+                                         tmp_bytes, &sb, &si, s));
+            HIPCHK(c, launch_screen_probe(a, sb, si, cus, s));
+        } else {
+            HIPCHK(c, launch_screen_probe(a, nullptr, nullptr, cus, s));
+        }
+        HIPCHK(c, launch_screen_reduce(a, s));
+    }
+    uint32_t e = 0, q = 0;
+    if (table) {
+        HIPCHK(c, hipMemcpyAsync(&e, c->d_err, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&q, c->tlk_bad.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (e & ERR_TAB_LOOKUP) {
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)(e & ~ERR_TAB_LOOKUP), 1, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, KMER_E_DEVICE, "read screen: the extent of bucket " + std::to_string(q) + " lies past the table");
+    }
+    return KMER_OK;
+}
+
+kmer_status kmer_table_screen_device(kmer_ctx *c, const void *d_bytes, size_t len, uint64_t min_count, uint32_t flags,
+                                     void *stream, const void **d_rows, uint64_t *n_reads) {
+    if (d_rows) *d_rows = nullptr;
+    if (n_reads) *n_reads = 0;
+    if (!c || !d_rows || !n_reads || (len && !d_bytes) || screen_bad_flags(flags)) return KMER_E_BAD_PARAM;
+    if (len == 0) return KMER_OK;
+    kmer_status st = screen_state(c);
+    if (st) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    HIPCHK(c, hipEventRecord(c->evw, (hipStream_t)stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
+    st = screen_run(c, (const uint8_t *)d_bytes, len, min_count, flags, n_reads);
+    if (st) {
+        *n_reads = 0;
+        return st;
+    }
+    *d_rows = *n_reads ? c->tsc_rows.p : nullptr;
+    return KMER_OK;
+}
+
+kmer_status kmer_table_screen(kmer_ctx *c, const uint8_t *bytes, size_t len, uint64_t min_count, uint32_t flags,
+                              kmer_read_screen *rows, uint64_t cap, uint64_t *n_reads) {
+    if (n_reads) *n_reads = 0;
+    if (!c || !n_reads || (len && !bytes) || (cap && !rows) || screen_bad_flags(flags)) return KMER_E_BAD_PARAM;
+    if (len == 0) return KMER_OK;
+    kmer_status st = screen_state(c);
+    if (st) return st;
+    const uint64_t n_nl = count_newlines(bytes, len);
+    const uint64_t n = n_nl ? (n_nl - 1) / 4 + 1 : 0;            // lines 1, 5, 9, .. of n_nl + 1
+    *n_reads = n;
+    if (cap < n) return fail(c, KMER_E_BAD_PARAM, "read screen: " + std::to_string(n) + " reads, room for " + std::to_string(cap));
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    hipStream_t s = c->stream;
+    const uint64_t batch = c->p.batch_bytes ? c->p.batch_bytes : SCREEN_BATCH;
+    uint64_t done = 0;
+    for (uint64_t pos = 0; pos < len;) {
+        // the piece: whole records (4 lines), as many as fit the batch, at least one
+        uint64_t e = pos, good = 0, cnt = 0;
+        bool more = false;
+        while (e < len) {
+            const void *nl = memchr(bytes + e, '\n', len - e);
+            if (!nl) break;
+            e = (uint64_t)((const uint8_t *)nl - bytes) + 1;
+            if ((++cnt & 3) != 0) continue;
+            if (e - pos <= batch || !good) good = e;
+            if (e - pos >= batch) {
+                more = true;
+                break;
+            }
+        }
+        if (!more && (len - pos <= batch || !good)) good = len;  // the input's tail
+        const uint64_t m = good - pos;
+        if (!screen_ensure(c->tsc_in, m, s)) return fail(c, KMER_E_OOM, "device allocation failed (read screen: input piece)");
+        st = upload(c, c->tsc_in.p, bytes + pos, m, s);
+        if (st) return st;
+        uint64_t np = 0;
+        st = screen_run(c, c->tsc_in.p, m, min_count, flags, &np);
+        if (st) return st;
+        if (done + np > n) return fail(c, KMER_E_DEVICE, "read screen: more rows than reads");
+        if (np) {
+            HIPCHK(c, hipMemcpyAsync(rows + done, c->tsc_rows.p, np * sizeof(ScreenRow), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        done += np;
+        pos = good;
+    }
+    if (done != n) return fail(c, KMER_E_DEVICE, "read screen: rows and reads differ");
+    return KMER_OK;
 }
 
 kmer_status kmer_table_routes(kmer_ctx *c, uint64_t *p1_fixed, uint64_t *p1_merged, uint64_t *p1_counted,

@@ -110,6 +110,13 @@ struct DBuf {
     }
 };
 
+// ensure() for a caller that reports a failed allocation as KMER_E_OOM and goes on (the read screen)
+template <typename T>
+inline bool screen_ensure(DBuf<T> &b, uint64_t n, hipStream_t s) {
+    if (b.ensure(n, s) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
 
 }  // namespace kmerhip
 
@@ -271,6 +278,13 @@ struct kmer_ctx {
     DBuf<unsigned long long> tab_hist;   // spectrum: AB_HIST_BINS bins, then [0..1] the last bin, [2] extract count / cursor
     DBuf<uint64_t> tex_code, tex_code2, tex_val, tex_val2;   // extract: (2-bit code, value) pairs and the sort's twins
     DBuf<uint8_t> tex_keys;        // extract: the sorted keys' bytes (valid until the next extract)
+    // read screen (kmer_screen.hip): a piece's window keys, codes and values, the sorted route's pairs, the rows
+    DBuf<uint64_t> tsc_h, tsc_val;
+    DBuf<uint8_t> tsc_code;
+    DBuf<uint32_t> tsc_bkt, tsc_bkt2, tsc_idx, tsc_idx2;
+    DBuf<ScreenRow> tsc_rows;      // one row per read (valid until the next screen)
+    DBuf<uint8_t> tsc_in;          // host call: one uploaded piece of the input
+    uint32_t t_nq = TAB_NQ;        // buckets the last table finish owns (an exchanged table: its rank's share)
     DBuf<unsigned long long> tjoin;   // set operations (kmer_setops.hip): [0..7] compare's sums, [8] setop count / cursor
     uint64_t t_lines = 0;          // a group: the input lines of its last count (kmer_table_extract)
     hipEvent_t tev[8] = {};        // table phase events

@@ -801,7 +801,7 @@ constexpr uint64_t TAB_SORT_GROUP_KEYS = 6144;          // sort final: keys of a
 hipError_t launch_tab_digest(const uint64_t *ent, const uint64_t *start, const uint32_t *nd, uint32_t k,
                             uint32_t narrow, unsigned long long *out,
                              hipStream_t s);
-// A finished table as its readers see it (kmer_lookup.hip, kmer_probe.hip);
+// A finished table as its readers see it (kmer_lookup.hip, kmer_probe.hip, kmer_screen.hip ...);
 // filled in one place, table_view (kmer_api.hip)
 struct TabView {
     const uint64_t *ent;           // the table: entries, TAB_NQ + 1 bucket starts, entries per bucket
@@ -841,6 +841,70 @@ struct TabProbe : TabView {
 };
 hipError_t tab_probe_temp_bytes(uint64_t m, size_t *bytes);
 hipError_t launch_tab_probe(const TabProbe &a, uint32_t n_cu, hipStream_t s);
+// Read screen against a finished table (kmer_screen.hip, kmer_table_screen):
+// every forward window w of every read is one probe, by its class {w, rc w}.
+// The weight of a window is the value its read's own Map gives the class's
+// keys: table mode -- the orientations that start with the prefix (a
+// self-complementary window counts for both strands: 2 if it starts with it);
+// canonical mode -- 1 if the class's smaller string starts with it.  cf / cr:
+// the planar codes of w and rc w.  *dbl: the table's count is doubled (table
+// mode, w == rc w), as tab_entry_keys doubles it.
+__host__ __device__ inline uint32_t screen_weight(uint64_t cf, uint64_t cr, uint32_t k, uint32_t plo, uint32_t phi,
+                                                  uint32_t pmask, bool canonical, bool *dbl) {
+    const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+    const uint32_t f = (((((uint32_t)cf & km) ^ plo) | (((uint32_t)(cf >> k) & km) ^ phi)) & pmask) == 0 ? 1u : 0u;
+    const uint32_t r = (((((uint32_t)cr & km) ^ plo) | (((uint32_t)(cr >> k) & km) ^ phi)) & pmask) == 0 ? 1u : 0u;
+    *dbl = false;
+    if (canonical) return tab_str_le(cf, cr, k) ? f : r;
+    if (cf == cr) {
+        *dbl = true;
+        return 2u * f;
+    }
+    return f + r;
+}
+// Window m of a line's bit planes (bit j of LO / HI: the low / high code bit
+// of byte j, as pass 1 forms them; m + k <= 64): the planar codes of w and rc w
+__host__ __device__ inline void screen_window_codes(uint64_t LO, uint64_t HI, uint32_t m, uint32_t k, uint64_t *cf,
+                                                    uint64_t *cr) {
+    const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+    const uint32_t flo = (uint32_t)(LO >> m) & km, fhi = (uint32_t)(HI >> m) & km;
+    const uint32_t rlo = __builtin_bitreverse32(~flo & km) >> (32 - k);
+    const uint32_t rhi = __builtin_bitreverse32(~fhi & km) >> (32 - k);
+    *cf = ((uint64_t)fhi << k) | flo;
+    *cr = ((uint64_t)rhi << k) | rlo;
+}
+// the one-byte code of a window: its weight (0, 1, 2), SC_DBL when the table's
+// count is doubled, or SC_SKIP (a byte outside A/C/G/T: a record key, not matched)
+constexpr uint8_t SC_WMASK = 3, SC_DBL = 4, SC_SKIP = 0x80;
+constexpr uint32_t SC_NS = 16;                         // consecutive windows per lane of the keys kernel
+constexpr uint32_t SC_BITS = TAB_L1 + TAB_L2 + 1;      // sort key: the bucket, or TAB_NQ (no probe)
+constexpr uint64_t SC_PIECE = 1ull << 26;              // windows per piece
+constexpr uint64_t SC_PIECE_TEST = 4096;               // ... with KMER_SCREEN_PIECE_TEST
+struct ScreenRow {                                     // (kmer_read_screen)
+    uint64_t windows, hits, skipped, sum;
+};
+struct TabScreen : TabView {
+    const uint8_t *data;           // the input: nothing outside [data, data + len) is loaded
+    uint64_t len;
+    const SeqLine *lines;          // by read (len 0: no windows)
+    const uint64_t *wbase2;        // by read: twice the index of its first window (scan of 2W)
+    uint64_t n_reads, total;       // reads, windows of all reads
+    uint64_t p0, m;                // the piece: windows [p0, p0 + m)
+    uint64_t *h;                   // by window of the piece: tab_key_h of its class
+    uint8_t *code;                 // ... its code (SC_*)
+    uint64_t *val;                 // ... the Map value of its class (0: absent or no probe)
+    uint32_t *bkt, *idx;           // sorted route: (bucket or TAB_NQ, window of the piece), or null
+    uint64_t min_count;            // >= 1
+    ScreenRow *rows;
+};
+hipError_t launch_screen_keys(const TabScreen &a, uint32_t n_cu, hipStream_t s);
+// sb / si: the piece's probes sorted by bucket (sorted route), or null: window order
+hipError_t launch_screen_probe(const TabScreen &a, const uint32_t *sb, const uint32_t *si, uint32_t n_cu,
+                               hipStream_t s);
+hipError_t launch_screen_reduce(const TabScreen &a, hipStream_t s);
+hipError_t screen_sort_bytes(uint64_t m, size_t *bytes);
+hipError_t launch_screen_sort(uint32_t *bkt, uint32_t *bkt2, uint32_t *idx, uint32_t *idx2, uint64_t m, void *tmp,
+                              size_t tmp_bytes, const uint32_t **sb, const uint32_t **si, hipStream_t s);
 // The by-value readers of a finished table (kmer_abundance.hip).  Spectrum:
 // hist[v] += the Map keys with value v, over the entries whose count is in
 // the 20-bit field (the host adds the big list and the record keys); counts

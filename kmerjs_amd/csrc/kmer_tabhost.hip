@@ -275,6 +275,7 @@ kmer_status table_finish(kmer_ctx *c, const uint64_t *B1, uint32_t qlo, uint32_t
     hipStream_t s = c->stream;
     c->t_canon = c->t_nkeys = c->t_sum = c->t_nbig = 0;
     c->t_done = true;
+    c->t_nq = qhi > qlo ? qhi - qlo : 1u;
     const uint64_t n = c->t_keys;
     if (n == 0) return KMER_OK;
     // the table is written over the pass-1 keys (dead after pass 2)
