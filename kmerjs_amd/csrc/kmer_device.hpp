@@ -22,6 +22,17 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
     return x;
 }
 
+// Inclusive wave64 prefix maximum (unsigned; 0 is the identity), same steps.
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true));   // row_shr:1
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true));   // row_shr:2
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true));   // row_shr:4
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true));   // row_shr:8
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false));  // row_bcast:15
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false));  // row_bcast:31
+    return x;
+}
+
 // lane i's value of v (i wave-uniform)
 __device__ __forceinline__ uint32_t readlane32(uint32_t v, uint32_t i) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
@@ -102,6 +113,10 @@ struct TileRegs {
     int hc;
 };
 
+// NT: the tile's own chunks with non-temporal loads -- for a kernel whose
+// input is read once per launch and is far larger than the caches (the halo
+// chunks, which the neighbouring tiles read as well, stay plain loads).
+template <bool NT = false>
 __device__ __forceinline__ void load_tile(const uint8_t *data, uint64_t len, int64_t g0, TileRegs &r) {
     const int tid = threadIdx.x;
     const bool halo = tid < NCH_FRONT + NCH_BACK;
@@ -113,7 +128,15 @@ __device__ __forceinline__ void load_tile(const uint8_t *data, uint64_t len, int
     if (g0 - FH >= 0 && (uint64_t)(g0 + TILE + BH) <= len) {
         const uint8_t *src = data + g0 + 16 * tid;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r.v[i] = *(const uint4 *)(src + 16 * TPB * i);
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (NT) {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 t = __builtin_nontemporal_load((const u32x4 *)(src + 16 * TPB * i));
+                r.v[i] = make_uint4(t.x, t.y, t.z, t.w);
+            } else {
+                r.v[i] = *(const uint4 *)(src + 16 * TPB * i);
+            }
+        }
         // every lane loads (lanes >= 9 repeat chunk 0): no divergent load, so no early wait
         r.vh = *(const uint4 *)(data + g0 - FH + 16 * (halo ? hc : 0));
     } else {

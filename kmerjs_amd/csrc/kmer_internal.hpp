@@ -102,6 +102,24 @@ struct HitRec {
 };
 constexpr int HMAX = 64;   // hit slots per tile (more go to the overflow list)
 
+// Tile-local line context of the tile position base + qrel (qrel 0..63) from
+// what the thread that scanned the 64 bytes at `base` knows: mask = its '\n'
+// bytes (bit i: byte base + i), pre = the tile's '\n' count before base,
+// prevnl = the tile position of the last '\n' before base (-1: none).
+// *c_local = '\n' count of the tile before the position, *lstart = one past
+// the last '\n' before it (-1: none in this tile).  A window that becomes a hit
+// record holds no '\n' and holds the position, so this is the context of the
+// window's start as well (HitRec::c_local / lstart).
+__host__ __device__ inline void region_line_context(uint32_t pre, int32_t prevnl, uint64_t mask, uint32_t qrel,
+                                                    int32_t base, uint32_t *c_local, int32_t *lstart) {
+    const uint64_t below = mask & ((1ull << qrel) - 1ull);
+    const uint32_t lo = (uint32_t)below, hi = (uint32_t)(below >> 32);
+    *c_local = pre + (uint32_t)__builtin_popcount(lo) + (uint32_t)__builtin_popcount(hi);
+    const int32_t own = hi ? 64 - __builtin_clz(hi) : 32 - __builtin_clz(lo | 1u);   // (below != 0: top bit + 1)
+    const int32_t ls = below ? base + own : prevnl + 1;
+    *lstart = ls > 0 ? ls : -1;
+}
+
 // Per-tile aggregates of the scan kernel, scanned (exclusive) across tiles
 // with TileSumOp: lines before the tile, start of the line open at the tile
 // start, hits before the tile.

@@ -338,13 +338,31 @@ struct alignas(16) ScanShared {
     uint32_t nx;                 // ... of which on lines that cross a tile edge
     uint32_t tcnt;               // real '\n' count of the tile
     uint32_t qn;                 // verified-hit queue fill
-    alignas(8) uint32_t q[QCAP]; // candidate words (byte kernel) / QCAP/2 {entry, mask} pairs (plane kernel)
+    alignas(8) uint32_t q[QCAP]; // candidate words
+};
+
+// The plane kernel's shared state.  A thread that holds candidates puts the
+// line context of its 64 bytes next to them (qc), so the candidate -> hit pass
+// looks nothing up: no per-chunk counts, no '\n' bitmap.
+constexpr uint32_t QE = QCAP / 2;   // queue entries of a round
+struct alignas(16) PlaneShared {
+    uint32_t wsum[TPB / 64];     // per-wave '\n' counts
+    uint32_t wmax[TPB / 64];     // per-wave last '\n' (tile position + 1, 0 = none)
+    uint32_t nh;                 // hit records written by this tile
+    uint32_t nx;                 // ... of which on lines that cross a tile edge
+    uint32_t tcnt;               // real '\n' count of the tile
+    uint32_t qn;                 // queue entries of the tile
+    uint2 q[QE];                 // {first window << 1 | strand, mask of 32 positions}
+    uint4 qc[QE];                // the entry's thread: {'\n' count before its region | (last '\n' before it + 1) << 16,
+                                 //                      '\n' mask of its 64 bytes (lo, hi), -}
+    uint32_t flat[2][64];        // waves 0 / 1: a batch of candidates, entry index << 16 | q << 1 | strand
 };
 
 // The tile's hit counts for the scan over the tile sums (thread 0, after the
 // tile's last hit record): an overflowed tile's hits all count as cross hits,
 // and a tile that may hold a long cross segment is flagged.
-__device__ __forceinline__ void put_tile_hits(const ScanArgs &a, const ScanShared &sh, uint32_t tile) {
+template <class SH>
+__device__ __forceinline__ void put_tile_hits(const ScanArgs &a, const SH &sh, uint32_t tile) {
     a.tsum[tile].nh = sh.nh;
     a.tsum[tile].nx = sh.nh > (uint32_t)HMAX ? sh.nh : sh.nx;   // overflowed: all hits cross
     if (sh.nh > (uint32_t)HMAX || (sh.nh && sh.tcnt == 0)) set_info(a.err, INFO_LONGSEG);
@@ -412,70 +430,6 @@ __device__ __forceinline__ void line_context_chunks(const uint8_t *buf, const Sc
     }
 }
 
-// bit i: byte i of a 16-byte chunk is '\n' (ASCII bytes).  Per word one
-// v_xad (bit 7 of a byte set: not '\n'), an and, and a v_dot4 whose weights
-// put the word's four flags side by side (times 128).
-__device__ __forceinline__ uint32_t chunk_nl_mask(uint4 x) {
-    const uint32_t k0a = 0x0A0A0A0Au, k7f = 0x7F7F7F7Fu;
-    const uint32_t lo = __builtin_amdgcn_udot4(not_nl_bits_xad(x.y, k0a, k7f), 0x80402010u,
-                            __builtin_amdgcn_udot4(not_nl_bits_xad(x.x, k0a, k7f), 0x08040201u, 0u, false), false);
-    const uint32_t hi = __builtin_amdgcn_udot4(not_nl_bits_xad(x.w, k0a, k7f), 0x80402010u,
-                            __builtin_amdgcn_udot4(not_nl_bits_xad(x.z, k0a, k7f), 0x08040201u, 0u, false), false);
-    return ~((lo >> 7) | (hi << 1)) & 0xFFFFu;
-}
-
-// The same for the plane kernel (sh.nlmap holds one bit per 64-byte thread
-// region; the chunks of a region are told apart by cpre), as ONE route for
-// every lane: the pass runs with a dozen lanes whose lines start at any
-// distance, so every branch of a case split would be executed anyway.
-//   round 1 (addresses depend on s0 only, issued with the window's reads):
-//            the chunk of s0-1, the cpre quad of its region, two bitmap words;
-//   round 2: the cpre quad (+ the next cpre) of the region R that holds the
-//            last '\n' before s0 -- s0's own region, or the highest bitmap
-//            bit below it;
-//   round 3: the chunk of R where cpre rises last, and its last '\n' before s0.
-// The two bitmap words reach 32..63 regions (2..4 KiB) back; a line that
-// starts further back walks the bitmap (a loop no FASTQ read enters).
-// want = false (window rejected, or s0 <= 0): c_local = 0, lstart = -1; the
-// reads are clamped into the tile, so such a lane is harmless.
-__device__ __forceinline__ void line_context_regions(const uint8_t *buf, const ScanShared &sh, int s0, bool want,
-                                                     uint32_t &c_local, int &lstart) {
-    const int cs = (s0 > 0 ? s0 - 1 : 0) >> 4;  // chunk holding byte s0-1
-    const int rg = cs >> 2, wi = rg >> 5;       // its region, the region's bitmap word
-    const uint4 x4 = *(const uint4 *)(buf + FH + 16 * cs);
-    const uint2 c2 = *(const uint2 *)(sh.cpre + 4 * rg);
-    const uint32_t mhi = sh.nlmap[wi], mlo = sh.nlmap[wi > 0 ? wi - 1 : 0];
-    // '\n' of chunk cs before s0 (a lane with s0 <= 0 counts garbage: not wanted)
-    const uint32_t cnt = __popc(__builtin_amdgcn_ubfe(chunk_nl_mask(x4), 0u, (uint32_t)(s0 - 16 * cs)));
-    const uint32_t ccs = (uint32_t)((((uint64_t)c2.y << 32) | c2.x) >> (16 * (cs & 3))) & 0xFFFFu;
-    const uint32_t cl = ccs + cnt;
-    const bool has = want && cl > 0;             // a '\n' before s0 in this tile
-    // R: s0's region if the '\n' is in chunk cs or in an earlier chunk of the
-    // region (cpre rose inside it), else the highest bitmap bit below rg
-    int R = rg;
-    if (has && cnt == 0 && ccs == (c2.x & 0xFFFFu)) {
-        const uint64_t m = (((uint64_t)mhi << 32) | (wi > 0 ? mlo : 0u)) & ((1ull << (32 + (rg & 31))) - 1ull);
-        R = 32 * (wi - 1) + 63 - (int)__clzll((long long)m);
-        if (m == 0) {                            // (cpre[4 * rg] > 0: an earlier word has a bit)
-            int w = wi - 1;
-            uint32_t mm;
-            do mm = sh.nlmap[--w]; while (mm == 0);
-            R = 32 * w + 31 - __clz(mm);
-        }
-    }
-    const uint2 d2 = *(const uint2 *)(sh.cpre + 4 * R);
-    const uint32_t nxt = sh.cpre[min(4 * R + 4, NCH_MAIN - 1)];   // (used for R < rg only: 4R + 4 <= 4rg)
-    const uint32_t d[4] = {d2.x & 0xFFFFu, d2.x >> 16, d2.y & 0xFFFFu, d2.y >> 16};
-    const int jl = R == rg ? cs - 4 * rg : 4;    // chunks [0, jl) of R lie before chunk cs
-    const int jc = (jl > 3 && d[3] < nxt) ? 3 : (jl > 2 && d[2] < d[3]) ? 2 : (jl > 1 && d[1] < d[2]) ? 1 : 0;
-    const int c = cnt ? cs : 4 * R + jc;
-    const uint4 y4 = *(const uint4 *)(buf + FH + 16 * c);
-    const uint32_t ym = __builtin_amdgcn_ubfe(chunk_nl_mask(y4), 0u, (uint32_t)min(s0 - 16 * c, 16));
-    const int last = 16 * c + 31 - __clz(ym);    // (has: ym != 0)
-    c_local = want ? cl : 0u;
-    lstart = has ? last + 1 : -1;
-}
-
 // One prefix hit (queue entry (q << 1) | strand): window analysis, tile-local
 // line context, hit record.
 // WIDE: k > 32 (the window's first k - 32 bases go to hits_hi / ovf_hi).
@@ -488,10 +442,15 @@ __device__ __forceinline__ void line_context_regions(const uint8_t *buf, const S
 // non-ACGT bytes alias.  The window's ACGT check settles it: if those pb
 // bytes (tile bytes [q, q + pb) on either strand) are all exactly A/C/G/T the
 // plane match is an exact match, else the candidate is dropped; prefix bytes
-// past the fifth are compared with pw (P words, then rc(P) words).
-template <bool THREAD_MAP, bool WIDE, uint32_t K = 0, uint32_t PLEN = 0>
-__device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, ScanShared &sh, uint32_t tile,
-                                         uint32_t e, uint32_t pb = 0, const uint32_t *pw = nullptr) {
+// past the fifth are compared with pw (P words, then rc(P) words).  lc is the
+// line context of the 64-byte region that holds q ({'\n' count of the tile
+// before it, its '\n' mask lo, hi, last '\n' before it + 1}), tcnt the tile's
+// '\n' count: q lies inside every window that becomes a record, and such a
+// window holds no '\n', so the context at q is the context at s0.
+template <bool THREAD_MAP, bool WIDE, uint32_t K = 0, uint32_t PLEN = 0, class SH>
+__device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, SH &sh, uint32_t tile,
+                                         uint32_t e, uint32_t pb = 0, const uint32_t *pw = nullptr,
+                                         uint4 lc = make_uint4(0u, 0u, 0u, 0u), uint32_t tcnt = 0) {
     static_assert((K == 0) == (PLEN == 0) && PLEN <= 5 && PLEN <= K && K <= (WIDE ? KMAX_TILE : KMAX_PACKED),
                   "fixed k / prefix length: both or neither, prefix fully plane-tested");
     const uint32_t k = K ? K : a.k, plen = K ? PLEN : a.plen;
@@ -558,12 +517,18 @@ __device__ __forceinline__ void emit_hit(const ScanArgs &a, const uint8_t *buf, 
     // the start of its line if that lies inside this tile
     uint32_t c_local = 0;
     int lstart = -1;
-    if (THREAD_MAP) line_context_regions(buf, sh, s0, valid && s0 > 0, c_local, lstart);
-    else if (valid && s0 > 0) line_context_chunks(buf, sh, s0, c_local, lstart);
+    if constexpr (THREAD_MAP) {
+        // one route for every lane; a rejected lane's values are not used
+        region_line_context(lc.x, (int)lc.w - 1, ((uint64_t)lc.z << 32) | lc.y, (uint32_t)q & 63u, q & ~63, &c_local,
+                            &lstart);
+    } else {
+        if (valid && s0 > 0) line_context_chunks(buf, sh, s0, c_local, lstart);
+        tcnt = sh.tcnt;
+    }
     // slots and the cross count: one LDS atomic per wave, not per hit.  The
     // hit kernel ranks hits of lines inside the tile; lines that cross a tile
     // edge are placed at finish (same predicate there).
-    const bool cross = valid && (lstart < 0 || c_local == sh.tcnt);
+    const bool cross = valid && (lstart < 0 || c_local == tcnt);
     const unsigned long long vm = __ballot(valid), xm = __ballot(cross), act = __ballot(1);
     const int lane = threadIdx.x & 63, leader = __ffsll((long long)act) - 1;
     uint32_t base = 0;
@@ -840,9 +805,9 @@ constexpr uint32_t PM_ATGAC = plane_masks_const("ATGAC", "GTCAT");
 // well (launch_scan_planes); the candidate -> hit-record pass is then
 // straight-line code.  0: a.k / a.plen at run time.
 template <bool FULL5, bool WIDE, uint32_t PM = 0, uint32_t K = 0, uint32_t PLEN = 0>
-__global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs pa) {
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(8))) void scan_planes_kernel(ScanArgs a, PlaneArgs pa) {
     __shared__ __attribute__((aligned(16))) uint8_t buf[BUFSZ];
-    __shared__ ScanShared sh;
+    __shared__ PlaneShared sh;
     __shared__ __attribute__((aligned(16))) uint8_t s_pr[2 * KMAX_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint64_t len = a.len;
@@ -856,9 +821,8 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
         uint8_t prb = 0;
         if (K == 0 && tid < 2 * KMAX_TILE) prb = a.PR[tid];
         TileRegs r;
-        load_tile(a.data, len, g0, r);
+        load_tile<true>(a.data, len, g0, r);
         if (tid == 0) {
-            sh.last_chunk = -1;
             sh.nh = 0;
             sh.nx = 0;
             sh.qn = 0;
@@ -873,33 +837,39 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     uint32_t w[17];
     load_thread_words(buf + FH + 64 * tid, w);
     const bool tail_tile = (uint64_t)(g0 + TILE) > len;
+    // '\n' mask of the 64 bytes, bit i = byte i: per word a v_xad (bit 7 of a
+    // byte set: not '\n') and an and, per pair of words a v_dot4 chain whose
+    // weights put the eight flags side by side (times 128: bits 7..14)
     const uint32_t k0a = 0x0A0A0A0Au, k7f = 0x7F7F7F7Fu;
-    uint32_t ccnt[4];
+    uint32_t nm[2];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        uint32_t cnt = 0;
-        if (!tail_tile) {
+    for (int h = 0; h < 2; ++h) {
+        uint32_t d[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) cnt += __popc(not_nl_bits_xad(w[4 * j + i], k0a, k7f));
-            cnt = 16u - cnt;
-        } else {
-            const int64_t gc = g0 + 64 * tid + 16 * j;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cnt += __popc(nl_flags_below(w[4 * j + i], (int64_t)len - (gc + 4 * i)));
-        }
-        ccnt[j] = cnt;
+        for (int p = 0; p < 4; ++p)
+            d[p] = __builtin_amdgcn_udot4(not_nl_bits_xad(w[8 * h + 2 * p + 1], k0a, k7f), 0x80402010u,
+                       __builtin_amdgcn_udot4(not_nl_bits_xad(w[8 * h + 2 * p], k0a, k7f), 0x08040201u, 0u, false), false);
+        nm[h] = ~((d[0] >> 7) | (d[1] << 1) | (d[2] << 9) | (d[3] << 17));
     }
-    const uint32_t ttot = ccnt[0] + ccnt[1] + ccnt[2] + ccnt[3];
-    {
-        const unsigned long long m = __ballot(ttot != 0);
-        if (lane == 0) {
-            sh.nlmap[2 * wid] = (uint32_t)m;
-            sh.nlmap[2 * wid + 1] = (uint32_t)(m >> 32);
-            if (m) atomicMax(&sh.last_chunk, 64 * wid + 63 - (int)__clzll((long long)m));   // (a thread index here)
-        }
+    if (tail_tile) {
+        // bytes at or past len are filler, not newlines to count
+        const int64_t left = (int64_t)len - (g0 + 64 * tid);
+        const uint64_t keep = left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1ull;
+        nm[0] &= (uint32_t)keep;
+        nm[1] &= (uint32_t)(keep >> 32);
     }
+    const uint32_t ttot = __popc(nm[0]) + __popc(nm[1]);
+    // my last '\n' as tile position + 1 (0: none); its exclusive max-scan is
+    // the last '\n' in front of my region, its block total the tile's
+    const uint32_t mylast = nm[1] ? 64u * (uint32_t)tid + 64u - (uint32_t)__clz(nm[1])
+                                  : nm[0] ? 64u * (uint32_t)tid + 32u - (uint32_t)__clz(nm[0]) : 0u;
     const uint32_t incl = wave_incl_sum(ttot);
-    if (lane == 63) sh.wsum[wid][0] = incl;
+    const uint32_t inclmax = wave_incl_max(mylast);
+    if (lane == 63) {
+        sh.wsum[wid] = incl;
+        sh.wmax[wid] = inclmax;
+    }
+    uint32_t prev1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inclmax, 0x138, 0xf, 0xf, true);   // wave_shr:1
 
     // ---- bit-planes of the 68 bytes: gL/gH groups of 8 bases (2 words) ----
     // y = low nibbles of x0, x1's low nibbles above them (v_bfi): byte i holds
@@ -959,49 +929,19 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     }
     if (!K && a.k < a.plen) mf[0] = mf[1] = mr[0] = mr[1] = 0;
 
-    // ---- block scan of the per-thread '\\n' counts -> cpre per chunk ----
-    __syncthreads();
-    {
-        uint32_t pre = incl - ttot, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < TPB / 64; ++ww) {
-            pre += ww < wid ? sh.wsum[ww][0] : 0u;
-            tot += sh.wsum[ww][0];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sh.cpre[4 * tid + j] = (uint16_t)pre;
-            pre += ccnt[j];
-        }
-        if (tid == 0) {
-            a.tsum[tile].cnt = tot;
-            sh.tcnt = tot;
-        }
-    }
-    __syncthreads();             // cpre visible
-    if (tid == 0) {
-        const int lt = sh.last_chunk;            // highest thread region with a '\\n'
-        int lp = -1;
-        if (lt >= 0) {
-            int c = 4 * lt + 3;
-            while ((c == NCH_MAIN - 1 ? sh.tcnt : (uint32_t)sh.cpre[c + 1]) == sh.cpre[c]) --c;
-            const int64_t lim = (int64_t)len - g0;
-            lp = last_newline_in_chunk(buf, c, lim < TILE ? (int)lim : TILE);
-        }
-        sh.lastpos = lp;
-        a.tsum[tile].lnl = lp >= 0 ? a.abs_offset + (uint64_t)(g0 + lp + 1) : 0;
-    }
-
     // ---- candidates -> LDS queue: one {first window, mask} entry per nonzero
     //      32-position mask (ballot + mbcnt, one LDS atomic per wave); the
     //      rare, branchy candidate -> hit-record pass runs once per tile in as
     //      few waves as possible.  The queue holds QE entries; a tile with
     //      more (short prefixes, repeats) is drained in rounds of QE (barrier,
-    //      drain, next QE entries), so the kernel holds the pass once ----
+    //      drain, next QE entries), so the kernel holds the pass once.  An
+    //      entry carries its thread's line context as far as the wave knows
+    //      it (qc); the draining wave adds the earlier waves' part, so no
+    //      barrier stands between the scans and the queue ----
     const uint32_t *pw = (const uint32_t *)s_pr;
-    uint2 *qe = (uint2 *)sh.q;
-    constexpr uint32_t QE = QCAP / 2;
-    static_assert(QE == 128 && QCAP == 256, "a round: one entry per thread of waves 0 and 1, 128 queue words each");
+    uint2 *qe = sh.q;
+    static_assert(QE == 128, "a round: one entry per thread of waves 0 and 1");
+    const uint4 myctx = make_uint4((incl - ttot) | (prev1 << 16), nm[0], nm[1], 0u);   // (both fields < 2^16: one wave's)
     const uint32_t mm[4] = {mf[0], mf[1], mr[0], mr[1]};
     uint32_t qpos[4] = {0, 0, 0, 0};             // queue position of entry hs (where mm[hs] != 0)
     {
@@ -1029,7 +969,10 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
 #pragma unroll
         for (int hs = 0; hs < 4; ++hs) {
             const uint32_t e0 = ((64u * (uint32_t)tid + 32u * (uint32_t)(hs & 1)) << 1) | (uint32_t)(hs >> 1);
-            if (mm[hs] && qpos[hs] - done < QE) qe[qpos[hs] - done] = make_uint2(e0, mm[hs]);
+            if (mm[hs] && qpos[hs] - done < QE) {
+                qe[qpos[hs] - done] = make_uint2(e0, mm[hs]);
+                sh.qc[qpos[hs] - done] = myctx;
+            }
         }
     };
     enqueue(0);
@@ -1039,28 +982,56 @@ __global__ __launch_bounds__(TPB) void scan_planes_kernel(ScanArgs a, PlaneArgs 
     // waves leave here -- before the loop, whose hoisted set-up they would
     // otherwise execute for nothing
     if (total <= 64 && wid != 0) return;
+    // the waves' '\n' counts and last '\n' (wave-uniform): what lies in front
+    // of each wave, the tile's count and the tile's last '\n'
+    uint32_t wpre[TPB / 64], wprev[TPB / 64], tcnt = 0, tlast = 0;
+    {
+        const uint4 ws = *(const uint4 *)sh.wsum, wm = *(const uint4 *)sh.wmax;
+        const uint32_t s[4] = {ws.x, ws.y, ws.z, ws.w}, m[4] = {wm.x, wm.y, wm.z, wm.w};
+#pragma unroll
+        for (int ww = 0; ww < TPB / 64; ++ww) {
+            wpre[ww] = tcnt;
+            wprev[ww] = tlast;
+            tcnt += (uint32_t)__builtin_amdgcn_readfirstlane((int)s[ww]);
+            tlast = max(tlast, (uint32_t)__builtin_amdgcn_readfirstlane((int)m[ww]));
+        }
+    }
+    if (tid == 0) {
+        a.tsum[tile].cnt = tcnt;
+        a.tsum[tile].lnl = tlast ? a.abs_offset + (uint64_t)(g0 + tlast) : 0;
+        sh.tcnt = tcnt;
+    }
     for (uint32_t done = 0;;) {                  // (uniform)
         // Entry tid of the round -> its candidates, one per lane: each wave
-        // spreads the set bits of its 64 entries over its own half of the
-        // queue (the entries are in registers by then), 64 candidates at a
-        // time, so a lane with two candidates does not make the wave run the
-        // pass twice.
+        // spreads the set bits of its 64 entries over its batch list (flat),
+        // 64 candidates at a time, so a lane with two candidates does not
+        // make the wave run the pass twice.  A candidate names its entry, whose
+        // line context its lane reads along with the window's bytes.
         const uint32_t left = total - done;
         uint2 en = make_uint2(0u, 0u);
         if ((uint32_t)tid < min(left, QE)) en = qe[tid];
         const uint32_t nc = __popc(en.y), incl = wave_incl_sum(nc);
         const uint32_t wtot = readlane32(incl, 63);
-        uint32_t *flat = sh.q + 128 * (wid & 1);
+        uint32_t *flat = sh.flat[wid & 1];
         for (uint32_t cb = 0; cb < wtot; cb += 64) {
             uint32_t m = en.y, p = incl - nc - cb;       // (wraps below cb: not in this batch)
             while (m) {
                 const uint32_t bit = __ffs(m) - 1;
                 m &= m - 1;
-                if (p < 64) flat[p] = en.x + (bit << 1);
+                if (p < 64) flat[p] = (en.x + (bit << 1)) | ((uint32_t)tid << 16);   // (q << 1 | strand < 2^15)
                 ++p;
             }
-            if ((uint32_t)lane < min(wtot - cb, 64u))
-                emit_hit<true, WIDE, K, PLEN>(a, buf, sh, tile, flat[lane], pb, pw);
+            if ((uint32_t)lane < min(wtot - cb, 64u)) {
+                const uint32_t f = flat[lane], ow = (f >> 13) & 3u;   // the wave that scanned q: q >> 12
+                uint4 lc = sh.qc[f >> 16];
+                // the earlier waves' part: their '\n' count, and their last '\n' where the wave has none before q's region
+                const uint32_t wp = ow == 0 ? wpre[0] : ow == 1 ? wpre[1] : ow == 2 ? wpre[2] : wpre[3];
+                const uint32_t wl = ow == 0 ? wprev[0] : ow == 1 ? wprev[1] : ow == 2 ? wprev[2] : wprev[3];
+                const uint32_t prv = lc.x >> 16;
+                lc.x = (lc.x & 0xFFFFu) + wp;
+                lc.w = prv ? prv : wl;
+                emit_hit<true, WIDE, K, PLEN>(a, buf, sh, tile, f & 0xFFFFu, pb, pw, lc, tcnt);
+            }
         }
         if (left <= QE) break;
         __syncthreads();         // the round's entries are read before the next round's are written
