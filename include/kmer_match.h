@@ -7,6 +7,9 @@
  *   ----------------------------------------------------  ---------------------------
  *   Redis kmer -> [template] lists, Mongo `reads`         kmer_db_open
  *     (src/kmerPyToMongo.py:21-42)
+ *   the ETL itself: genomes -> each template's k-mer      kmer_db_open_fasta
+ *     set, `lengths`, `ulength`, names                    (+ kmer_db_template_stats / _kmers / _name)
+ *     (src/kmerPyToMongo.py, offline, over pickles)
  *   findKmersMatchesRedis: one lrange per query k-mer,    kmer_match_open
  *     templates scored in first-hit order                 (+ kmer_match_templates)
  *     (lib/kmerFinderServer.js:171-226)
@@ -53,6 +56,73 @@ typedef struct kmer_match kmer_match;
  * offsets. */
 kmer_status kmer_db_open(int32_t device, uint32_t k, const char *keys, uint64_t n_keys,
                          const uint64_t *template_start, uint32_t n_templates, kmer_db **out);
+/* Template DB straight from FASTA genomes, built on the device of `ctx` (the
+ * replacement of the offline ETL).  The input is FASTA under the rules of
+ * KMER_FLAG_FASTA (kmer_api.h: header lines, a headerless first record, lines
+ * joined, one trailing '\r' per line dropped, empty lines add nothing, a
+ * sequence of length <= 1 is not counted), whether or not the context has that
+ * flag.  Record r of the input, in input order, is template r -- records
+ * without k-mers included, so template indices are record ordinals.  The
+ * k-mers of template r are the A/C/G/T keys of the record's own Map: the Map
+ * the context's configuration (k, prefix, KMER_FLAG_CANONICAL or not, step 1)
+ * builds from a file holding that record alone --
+ *   not canonical: for every forward window w of the sequence, key w if w
+ *                  starts with the prefix, and key rc w if rc w does;
+ *   canonical:     the smaller string of {w, rc w}, if it starts with the prefix.
+ * A window with a byte outside upper-case A/C/G/T gives no key (those are
+ * record keys; the DB has none).  lengths[r] (kmer_db_template_stats) = the sum
+ * of that Map's values over its A/C/G/T keys: one per (window, key) above, a
+ * self-complementary window of a non-canonical configuration gives 2;
+ * ulength[r] = the distinct such keys = the template's entries in the DB.
+ *
+ * `ctx` supplies k, the prefix, canonical or not, the device, the stream and
+ * the scratch (its FASTA rewrite and line finder): any single-device context,
+ * default ordered, KMER_FLAG_UNORDERED or KMER_FLAG_CANONICAL.  A chunk in
+ * flight is settled first; the call may come before any session or after a
+ * finish, and between stats, digest, lookup, screen, spectrum, extract, setops
+ * and match calls: the context's finished results (host and device result,
+ * table, bucket index, big list, extract buffers), kmer_lines, its records and
+ * its session position are left unchanged.  The DB is independent of the
+ * context (which may be reset or closed) and everything kmer_match_* does with
+ * a DB works on it.
+ * Checked before any device call -- KMER_E_BAD_PARAM: NULL ctx or out, NULL
+ * bytes with len > 0, an unknown flag bit, k > 32, step != 1; KMER_E_STATE: a
+ * group context, a session that has fed chunks and is not finished.
+ * len == 0: KMER_OK and a DB of 0 templates.  A prefix with a byte outside
+ * A/C/G/T, or longer than k: a valid DB whose templates all have ulength 0.
+ * KMER_E_NONASCII as for a feed, KMER_E_OOM: the context stays usable.  2^32 - 1
+ * or more window keys (before the dedup) or 2^31 - 1 or more templates:
+ * KMER_E_BAD_PARAM with kmer_db_open's messages.  On any failure *out is NULL
+ * and nothing is held.
+ *
+ * kmer_db_open_fasta_device: the bytes are in device memory, start at a record
+ * start (offset 0 of a FASTA, or a '>' after '\n'), may end without '\n' and
+ * may sit at any byte alignment; nothing outside [d_bytes, d_bytes + len) is
+ * loaded.  The call waits for the work queued so far on `stream` (as the
+ * lookup does); the DB is complete when it returns.
+ * kmer_db_open_fasta: host bytes, uploaded in pieces cut before header lines
+ * (the context's batch_bytes, default 64 MiB; a record longer than that is a
+ * piece of its own): device and pinned memory are bounded by the piece plus
+ * the (k-mer, template) pairs gathered so far; template indices run through
+ * all pieces. */
+enum { KMER_DB_PIECE_TEST = 1u };   /* debug: internal pieces of 4,096 windows, as KMER_SCREEN_PIECE_TEST */
+kmer_status kmer_db_open_fasta_device(kmer_ctx *ctx, const void *d_bytes, size_t len, uint32_t flags,
+                                      void *stream, kmer_db **out);
+kmer_status kmer_db_open_fasta(kmer_ctx *ctx, const uint8_t *bytes, size_t len, uint32_t flags, kmer_db **out);
+/* Per template, for templates [first, first + n) of any DB (either array may
+ * be NULL): ulengths = its entries after the dedup; lengths = as defined above
+ * for a FASTA DB, the number of keys the caller passed for it for a
+ * kmer_db_open DB.  KMER_E_BAD_PARAM for a range past the DB's templates. */
+kmer_status kmer_db_template_stats(kmer_db *db, uint32_t first, uint32_t n, uint64_t *lengths, uint64_t *ulengths);
+/* The k-mers of template `tmpl` as ascending indices into the DB's distinct
+ * k-mers (kmer_db_kmers decodes them), computed on the device from the
+ * k-mer -> templates lists (no transpose is kept).  Up to `cap` entries;
+ * *n = their number (the template's ulength). */
+kmer_status kmer_db_template_kmers(kmer_db *db, uint32_t tmpl, uint64_t cap, uint32_t *idx, uint64_t *n);
+/* The name of template `tmpl`: its header line without '>' and without the
+ * trailing '\r' -- *len bytes at *name, owned by the DB (not terminated at
+ * *len).  Length 0 for a headerless record and for a kmer_db_open DB. */
+kmer_status kmer_db_template_name(const kmer_db *db, uint32_t tmpl, const char **name, uint32_t *len);
 /* distinct = distinct k-mers, entries = (k-mer, template) pairs after dedup. */
 kmer_status kmer_db_info(const kmer_db *db, uint32_t *k, uint32_t *n_templates, uint64_t *distinct,
                          uint64_t *entries);

@@ -60,11 +60,14 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
-MATCH_EXPORTS = ["kmer_db_open", "kmer_db_info", "kmer_db_kmers", "kmer_db_close", "kmer_match_open",
+MATCH_EXPORTS = ["kmer_db_open", "kmer_db_open_fasta_device", "kmer_db_open_fasta", "kmer_db_template_stats",
+                 "kmer_db_template_kmers", "kmer_db_template_name",
+                 "kmer_db_info", "kmer_db_kmers", "kmer_db_close", "kmer_match_open",
                  "kmer_match_open_device", "kmer_match_open_table",
                  "kmer_match_info", "kmer_match_templates", "kmer_match_template_kmers", "kmer_match_winner", "kmer_match_remove",
                  "kmer_match_removed", "kmer_match_close", "kmer_match_last_error"]
 EXPORTS = EXPORTS + MATCH_EXPORTS
+DB_PIECE_TEST = 1      # kmer_db_open_fasta* (KMER_DB_PIECE_TEST): debug, internal pieces of 4,096 windows
 ORDER_FIRST_HIT = 0    # kmer_match_templates: the Redis path's templates Map order
 ORDER_DB = 1           # the Mongo aggregation's (DB) order
 
@@ -178,6 +181,12 @@ def _load():
         "kmer_version": (ctypes.c_char_p, []),
         "kmer_db_open": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, vp, u64, pu64, ctypes.c_uint32,
                                         ctypes.POINTER(vp)]),
+        "kmer_db_open_fasta_device": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_uint32, vp, ctypes.POINTER(vp)]),
+        "kmer_db_open_fasta": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(vp)]),
+        "kmer_db_template_stats": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, pu64, pu64]),
+        "kmer_db_template_kmers": (ctypes.c_int, [vp, ctypes.c_uint32, u64, ctypes.POINTER(ctypes.c_uint32), pu64]),
+        "kmer_db_template_name": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(vp),
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
         "kmer_db_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), pu64,
                                         pu64]),
         "kmer_db_close": (ctypes.c_int, [vp]),
@@ -282,7 +291,7 @@ class Counter:
         if st != KMER_OK:
             raise KmerError(st, "kmer_open(k=%d, step=%d, prefix=%r)" % (k, step, prefix))
         self.h = h
-        self.k, self.step = k, step
+        self.k, self.step, self.device = k, step, device
 
     def _check(self, st, what):
         if st != KMER_OK:

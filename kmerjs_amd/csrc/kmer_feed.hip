@@ -954,6 +954,7 @@ kmer_status feed(kmer_ctx *c, const uint8_t *d, uint64_t len, hipStream_t s) {
         if (st) return st;
     }
     if (len == 0) return KMER_OK;
+    c->session_fed = true;
     const uint64_t n_tiles64 = (len + TILE - 1) / TILE;
     if (n_tiles64 > 0x7FFFFFFFull) return fail(c, KMER_E_BAD_PARAM, "chunk too large");
     const uint32_t n_tiles = (uint32_t)n_tiles64;
@@ -999,6 +1000,7 @@ kmer_status reset(kmer_ctx *c) {
     for (double &x : c->t_ms) x = 0.0;
     c->scan_ms = c->feed_ms = c->finish_ms = 0.0;
     c->open_stream = true;
+    c->session_fed = false;
     return KMER_OK;
 }
 

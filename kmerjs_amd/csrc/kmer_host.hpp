@@ -217,6 +217,7 @@ struct kmer_ctx {
     // host side
     uint64_t abs_offset = 0;
     bool open_stream = false;      // reset called, not finished
+    bool session_fed = false;      // ... and a chunk was fed since (kmer_db_open_fasta: KMER_E_STATE)
     std::unordered_map<std::string, Ent> exotic;
     uint64_t *h_small = nullptr;   // pinned (24 words): [0..7] copy of d_scal, [8..11] pos, [12..17] table feed
     uint64_t *h_tail = nullptr;    // pinned, mapped, coherent (TAIL_*): d_scal[0..7] written by the chunk tail kernel, ...

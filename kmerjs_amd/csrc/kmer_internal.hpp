@@ -923,6 +923,57 @@ hipError_t launch_screen_reduce(const TabScreen &a, hipStream_t s);
 hipError_t screen_sort_bytes(uint64_t m, size_t *bytes);
 hipError_t launch_screen_sort(uint32_t *bkt, uint32_t *bkt2, uint32_t *idx, uint32_t *idx2, uint64_t m, void *tmp,
                               size_t tmp_bytes, const uint32_t **sb, const uint32_t **si, hipStream_t s);
+// Template DB from FASTA (kmer_dbfasta.hip, kmer_db_open_fasta): every forward
+// window w of every record's joined sequence gives the A/C/G/T keys of "the
+// record's own Map" as the matcher's 2-bit codes.  The keys of a window, from
+// the planar codes of w and rc w: their number is the window's weight
+// (screen_weight: the value the record's Map gains by it), so a
+// self-complementary window of a non-canonical configuration gives its one key
+// twice (the DB's dedup drops the repeat; `lengths` counts both).
+__host__ __device__ inline uint32_t dbf_window_keys(uint64_t cf, uint64_t cr, uint32_t k, uint32_t plo, uint32_t phi,
+                                                    uint32_t pmask, bool canonical, uint64_t keys[2]) {
+    bool dbl;
+    const uint32_t wt = screen_weight(cf, cr, k, plo, phi, pmask, canonical, &dbl);
+    if (wt == 0) return 0;
+    if (canonical) {
+        keys[0] = tab_planar_code2(tab_str_le(cf, cr, k) ? cf : cr, k);
+    } else if (wt == 2) {                               // (both orientations start with the prefix, or w == rc w)
+        keys[0] = tab_planar_code2(cf, k);
+        keys[1] = tab_planar_code2(cr, k);
+    } else {                                            // the one orientation that starts with the prefix
+        const uint32_t km = k >= 32 ? ~0u : ((1u << k) - 1u);
+        const bool f = (((((uint32_t)cf & km) ^ plo) | (((uint32_t)(cf >> k) & km) ^ phi)) & pmask) == 0;
+        keys[0] = tab_planar_code2(f ? cf : cr, k);
+    }
+    return wt;
+}
+constexpr uint32_t DBF_NS = 16;                        // consecutive windows per lane (as SC_NS)
+constexpr uint64_t DBF_PIECE = 1ull << 26;             // windows per piece
+constexpr uint64_t DBF_PIECE_TEST = 4096;              // ... with KMER_DB_PIECE_TEST
+struct DbFasta {
+    const uint8_t *data;           // the rewritten FASTA: nothing outside [data, data + len) is loaded
+    uint64_t len;
+    const SeqLine *lines;          // by record (len 0: no windows)
+    const uint64_t *wbase2;        // by record: twice the index of its first window (scan of 2W)
+    uint64_t n_rec, total;         // records, windows of all records
+    uint64_t p0, m;                // the piece: windows [p0, p0 + m)
+    uint32_t k, plo, phi, pmask, canonical;
+    uint32_t t0;                   // template index of record 0
+    uint32_t *cnt;                 // count pass: keys of each lane's windows (one per DBF_NS windows of the piece)
+    const uint64_t *off;           // write pass: their exclusive scan
+    uint64_t *codes;               // write pass: the piece's pairs, in window order
+    uint32_t *tmpl;
+    uint64_t n_pairs;              // pairs of the piece (the scan's total)
+    uint64_t *lengths;             // by record: pairs so far (a record cut by a piece edge adds up over the pieces)
+};
+hipError_t launch_dbf_keys(const DbFasta &a, bool write, uint32_t n_cu, hipStream_t s);
+hipError_t launch_dbf_lengths(const DbFasta &a, hipStream_t s);
+// the records' header lines in the rewritten FASTA: nlen[r] = bytes of record
+// r's name (the header without '>'), then gathered back to back at noff[r]
+hipError_t launch_dbf_name_lens(const uint8_t *data, uint64_t len, const SeqLine *lines, uint64_t n_rec,
+                                uint64_t *nlen, hipStream_t s);
+hipError_t launch_dbf_names(const uint8_t *data, const SeqLine *lines, uint64_t n_rec, const uint64_t *noff,
+                            const uint64_t *nlen, uint8_t *out, hipStream_t s);
 // The by-value readers of a finished table (kmer_abundance.hip).  Spectrum:
 // hist[v] += the Map keys with value v, over the entries whose count is in
 // the 20-bit field (the host adds the big list and the record keys); counts
@@ -1088,5 +1139,28 @@ struct TabOwner {
     bool empty;                    // a finish with no keys: the view is not filled
 };
 int table_view(kmer_ctx *c, TabView *v, TabOwner *o);
+
+// The (2-bit code, template) pairs of FASTA genomes for the matcher
+// (kmer_dbfasta.hip; kmer_db_open_fasta*): gathered with the context's FASTA
+// rewrite, line finder, stream and scratch, template-major, duplicates
+// included, complete (the context's stream waited for) on return.  The arrays
+// are the caller's: dbfasta_release.  Returns a kmer_status; on a failure
+// nothing is held and the message is the context's last error.
+struct DbFastaPairs {
+    int device;
+    uint32_t k;
+    uint64_t *codes;               // device, n
+    uint32_t *tmpl;
+    uint64_t n, cap;
+    uint32_t nt;                   // records = templates
+    uint64_t *lengths;             // host (malloc), nt: pairs per template
+    char *names;                   // host (malloc): the names back to back
+    uint64_t *name_off;            // host (malloc), nt + 1
+};
+// the state checks that need the context (k, step, group, open session): before any device call
+int dbfasta_check(kmer_ctx *c);
+int dbfasta_gather(kmer_ctx *c, const uint8_t *bytes, uint64_t len, bool on_device, uint32_t flags, void *stream,
+                   DbFastaPairs *out);
+void dbfasta_release(DbFastaPairs *p);
 
 }  // namespace kmerhip

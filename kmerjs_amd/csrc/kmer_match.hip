@@ -9,6 +9,11 @@
 //   DB (once):  k-mers packed to 2-bit codes, (code, template) pairs radix
 //               sorted (stable: a k-mer's templates stay in DB order), dedup,
 //               CSR: U[m] sorted distinct codes, O[m + 1] list offsets, T[] templates.
+//               The pairs come from the caller's host strings (kmer_db_open:
+//               upload + pack) or from FASTA genomes on the device
+//               (kmer_db_open_fasta*: kmer_dbfasta.hip gathers them over a
+//               counting context); everything from the sort on is shared
+//               (build_from_pairs).
 //   round 1:    each query key packed and binary-searched in U; hits expanded to
 //               (template, query) pairs in (query, list) order, radix sorted by
 //               template (stable) -> per-template segments of query indices:
@@ -28,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -370,6 +376,22 @@ __global__ void db_decode_kernel(const uint64_t *U, uint64_t first, uint64_t n, 
     }
 }
 
+// DB k-mer i has template t in its (ascending) list
+struct HasTemplate {
+    const uint64_t *O;
+    const uint32_t *T;
+    uint32_t t;
+    __device__ bool operator()(uint32_t i) const {
+        uint64_t lo = O[i], hi = O[i + 1];
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (T[mid] < t) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo < O[i + 1] && T[lo] == t;
+    }
+};
+
 uint32_t grid_for(uint64_t n, uint32_t block = 256, uint32_t cap = 65536) {
     const uint64_t g = (n + block - 1) / block;
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
@@ -412,6 +434,9 @@ struct kmer_db {
     bool has_spare = false;
     uint32_t live = 0;                         // open matches
     bool closing = false;                      // kmer_db_close called while matches were open
+    // per template (host): keys handed in / FASTA window keys, entries after dedup, names (FASTA DBs)
+    std::vector<uint64_t> lengths, ulengths, name_off;
+    std::string names;
 };
 
 struct kmer_match {
@@ -451,45 +476,35 @@ void free_db(kmer_db *db) {
     delete db;
 }
 
-kmer_status build_db(kmer_db *db, const char *keys, uint64_t n, const uint64_t *ts) {
+// The DB from n (code, template) pairs in device memory, duplicates included,
+// a k-mer's templates in ascending order among its pairs (template-major input
+// and the stable sort): sort, dedup, CSR, directory, entries per template.  c
+// and t are sorted in place (they stay the caller's); queued on the DB's
+// stream, which the caller's writers of c and t must have been waited for.
+kmer_status build_from_pairs(kmer_db *db, uint64_t *c, uint32_t *t, uint64_t n) {
     hipStream_t s = db->s;
     Temp tmp;
-    uint8_t *dkeys = nullptr;
-    uint64_t *c = nullptr, *c2 = nullptr, *dts = nullptr, *pos = nullptr;
-    uint32_t *t = nullptr, *t2 = nullptr, *bad = nullptr;
+    uint64_t *c2 = nullptr, *pos = nullptr, *seg = nullptr;
+    uint32_t *t2 = nullptr, *e1 = nullptr, *e2 = nullptr;
     auto cleanup = [&]() {
-        for (void *p : {(void *)dkeys, (void *)c, (void *)c2, (void *)dts, (void *)pos, (void *)t, (void *)t2,
-                        (void *)bad})
+        (void)hipStreamSynchronize(s);
+        for (void *p : {(void *)c2, (void *)pos, (void *)seg, (void *)t2, (void *)e1, (void *)e2})
             if (p) (void)hipFree(p);
     };
     struct Guard {
         decltype(cleanup) &f;
         ~Guard() { f(); }
     } guard{cleanup};
-    MCHK(dalloc(&dkeys, n * db->k));
-    MCHK(dalloc(&c, n));
+    db->ulengths.assign(db->nt, 0);
+    if (n == 0) {
+        MCHK(dalloc(&db->O, 1));
+        MCHK(hipMemsetAsync(db->O, 0, 8, s));
+        MCHK(hipStreamSynchronize(s));
+        return KMER_OK;
+    }
     MCHK(dalloc(&c2, n));
-    MCHK(dalloc(&t, n));
     MCHK(dalloc(&t2, n));
-    MCHK(dalloc(&dts, (uint64_t)db->nt + 1));
     MCHK(dalloc(&pos, n));
-    MCHK(dalloc(&bad, 1));
-    MCHK(hipMemsetAsync(bad, 0, 4, s));
-    // (the caller's arrays, read in place: waited for on every return path)
-    struct SyncOnExit {
-        hipStream_t s;
-        ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } wait_uploads{s};
-    MCHK(hipMemcpyAsync(dkeys, keys, n * db->k, hipMemcpyHostToDevice, s));
-    MCHK(hipMemcpyAsync(dts, ts, ((uint64_t)db->nt + 1) * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(db_pack_kernel, dim3(grid_for(n)), dim3(256), 0, s, dkeys, n, db->k, c, bad);
-    hipLaunchKernelGGL(db_tmpl_kernel, dim3(std::min<uint32_t>(std::max<uint32_t>(db->nt, 1), 65536)), dim3(256), 0,
-                       s, dts, db->nt, t);
-    MCHK(hipGetLastError());
-    uint32_t hbad = 0;
-    MCHK(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    if (hbad) return set_err(KMER_E_BAD_PARAM, "kmer_db_open: a template k-mer has a byte outside A/C/G/T");
     rocprim::double_buffer<uint64_t> kb(c, c2);
     rocprim::double_buffer<uint32_t> vb(t, t2);
     MROC(tmp, rocprim::radix_sort_pairs(t, b, kb, vb, (size_t)n, 0, 2 * db->k, s));
@@ -529,8 +544,64 @@ kmer_status build_db(kmer_db *db, const char *keys, uint64_t n, const uint64_t *
     hipLaunchKernelGGL(db_dir_kernel, dim3(grid_for(np + 1)), dim3(256), 0, s, db->U, db->m, db->dlo, db->dsh, np,
                        db->dir);
     MCHK(hipGetLastError());
+    // entries per template (kmer_db_template_stats): T sorted, a search per template
+    if (db->nt) {
+        MCHK(dalloc(&e1, db->entries));
+        MCHK(dalloc(&e2, db->entries));
+        MCHK(dalloc(&seg, (uint64_t)db->nt + 1));
+        MCHK(hipMemcpyAsync(e1, db->T, db->entries * 4, hipMemcpyDeviceToDevice, s));
+        rocprim::double_buffer<uint32_t> eb(e1, e2);
+        MROC(tmp, rocprim::radix_sort_keys(t, b, eb, (size_t)db->entries, 0, std::max(1, bit_width64(db->nt)), s));
+        hipLaunchKernelGGL(q_seg_kernel, dim3(grid_for((uint64_t)db->nt + 1)), dim3(256), 0, s, eb.current(),
+                           db->entries, db->nt, seg);
+        MCHK(hipGetLastError());
+        std::vector<uint64_t> hseg((size_t)db->nt + 1);
+        MCHK(hipMemcpyAsync(hseg.data(), seg, hseg.size() * 8, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < db->nt; ++i) db->ulengths[i] = hseg[i + 1] - hseg[i];
+    }
     MCHK(hipStreamSynchronize(s));
     return KMER_OK;
+}
+
+// kmer_db_open: the caller's strings uploaded and packed, template t owning [ts[t], ts[t + 1])
+kmer_status build_db(kmer_db *db, const char *keys, uint64_t n, const uint64_t *ts) {
+    hipStream_t s = db->s;
+    uint8_t *dkeys = nullptr;
+    uint64_t *c = nullptr, *dts = nullptr;
+    uint32_t *t = nullptr, *bad = nullptr;
+    auto cleanup = [&]() {
+        for (void *p : {(void *)dkeys, (void *)c, (void *)dts, (void *)t, (void *)bad})
+            if (p) (void)hipFree(p);
+    };
+    struct Guard {
+        decltype(cleanup) &f;
+        ~Guard() { f(); }
+    } guard{cleanup};
+    MCHK(dalloc(&dkeys, n * db->k));
+    MCHK(dalloc(&c, n));
+    MCHK(dalloc(&t, n));
+    MCHK(dalloc(&dts, (uint64_t)db->nt + 1));
+    MCHK(dalloc(&bad, 1));
+    MCHK(hipMemsetAsync(bad, 0, 4, s));
+    {
+        // (the caller's arrays, read in place: waited for on every return path)
+        struct SyncOnExit {
+            hipStream_t s;
+            ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+        } wait_uploads{s};
+        MCHK(hipMemcpyAsync(dkeys, keys, n * db->k, hipMemcpyHostToDevice, s));
+        MCHK(hipMemcpyAsync(dts, ts, ((uint64_t)db->nt + 1) * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(db_pack_kernel, dim3(grid_for(n)), dim3(256), 0, s, dkeys, n, db->k, c, bad);
+        hipLaunchKernelGGL(db_tmpl_kernel, dim3(std::min<uint32_t>(std::max<uint32_t>(db->nt, 1), 65536)), dim3(256),
+                           0, s, dts, db->nt, t);
+        MCHK(hipGetLastError());
+        uint32_t hbad = 0;
+        MCHK(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        if (hbad) return set_err(KMER_E_BAD_PARAM, "kmer_db_open: a template k-mer has a byte outside A/C/G/T");
+    }
+    return build_from_pairs(db, c, t, n);
 }
 
 // The arrays of a match build (every open): per query index and per template.
@@ -711,19 +782,119 @@ kmer_status kmer_db_open(int32_t device, uint32_t k, const char *keys, uint64_t 
         delete db;
         MCHK(e);
     }
-    kmer_status st = KMER_OK;
-    if (n_keys) {
-        st = build_db(db, keys, n_keys, template_start);
-    } else {
-        e = dalloc(&db->O, 1);
-        if (e == hipSuccess) e = hipMemset(db->O, 0, 8);
-        if (e != hipSuccess) st = set_err(KMER_E_DEVICE, "kmer_db_open: allocation failed");
-    }
+    db->lengths.resize(n_templates);
+    for (uint32_t t = 0; t < n_templates; ++t) db->lengths[t] = template_start[t + 1] - template_start[t];
+    db->name_off.assign((size_t)n_templates + 1, 0);
+    const kmer_status st = n_keys ? build_db(db, keys, n_keys, template_start) : build_from_pairs(db, nullptr, nullptr, 0);
     if (st != KMER_OK) {
         free_db(db);
         return st;
     }
     *out = db;
+    return KMER_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// kmer_db_open_fasta*: the pairs gathered over the context (kmer_dbfasta.hip), then the shared build
+kmer_status open_fasta(kmer_ctx *ctx, const uint8_t *bytes, size_t len, bool on_device, uint32_t flags, void *stream,
+                       kmer_db **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (len && !bytes) || (flags & ~(uint32_t)KMER_DB_PIECE_TEST))
+        return set_err(KMER_E_BAD_PARAM, "kmer_db_open_fasta: NULL argument or unknown flag");
+    kmerhip::DbFastaPairs p;
+    kmer_status st = (kmer_status)kmerhip::dbfasta_gather(ctx, bytes, len, on_device, flags, stream, &p);
+    if (st != KMER_OK) return set_err(st, std::string("kmer_db_open_fasta: ") + kmer_last_error(ctx));
+    struct Release {
+        kmerhip::DbFastaPairs *p;
+        ~Release() { kmerhip::dbfasta_release(p); }
+    } release{&p};
+    MCHK(hipSetDevice(p.device));
+    kmer_db *db = new kmer_db();
+    db->device = p.device;
+    db->k = p.k;
+    db->nt = p.nt;
+    hipError_t e = hipStreamCreateWithFlags(&db->s, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete db;
+        MCHK(e);
+    }
+    if (p.nt) {
+        db->lengths.assign(p.lengths, p.lengths + p.nt);
+        db->name_off.assign(p.name_off, p.name_off + p.nt + 1);
+        db->names.assign(p.names, p.name_off[p.nt]);
+    } else {
+        db->name_off.assign(1, 0);
+    }
+    st = build_from_pairs(db, p.codes, p.tmpl, p.n);     // (the gather waited for the context's stream)
+    if (st != KMER_OK) {
+        free_db(db);
+        return st;
+    }
+    *out = db;
+    return KMER_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+kmer_status kmer_db_open_fasta_device(kmer_ctx *ctx, const void *d_bytes, size_t len, uint32_t flags, void *stream,
+                                      kmer_db **out) {
+    return open_fasta(ctx, (const uint8_t *)d_bytes, len, true, flags, stream, out);
+}
+
+kmer_status kmer_db_open_fasta(kmer_ctx *ctx, const uint8_t *bytes, size_t len, uint32_t flags, kmer_db **out) {
+    return open_fasta(ctx, bytes, len, false, flags, nullptr, out);
+}
+
+kmer_status kmer_db_template_stats(kmer_db *db, uint32_t first, uint32_t n, uint64_t *lengths, uint64_t *ulengths) {
+    if (!db || first > db->nt || n > db->nt - first)
+        return set_err(KMER_E_BAD_PARAM, "kmer_db_template_stats: NULL db or a range past the DB's templates");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (lengths) lengths[i] = db->lengths[first + i];
+        if (ulengths) ulengths[i] = db->ulengths[first + i];
+    }
+    return KMER_OK;
+}
+
+kmer_status kmer_db_template_kmers(kmer_db *db, uint32_t tmpl, uint64_t cap, uint32_t *idx, uint64_t *n) {
+    if (!db || !n || tmpl >= db->nt || (cap && !idx))
+        return set_err(KMER_E_BAD_PARAM, "kmer_db_template_kmers: bad argument");
+    const uint64_t ul = db->ulengths[tmpl];
+    *n = ul;
+    if (!ul || !cap) return KMER_OK;
+    MCHK(hipSetDevice(db->device));
+    hipStream_t s = db->s;
+    // count + compact over the DB's distinct k-mers (ascending): those whose list holds the template
+    uint32_t *d = nullptr;
+    unsigned long long *dn = nullptr;
+    auto body = [&]() -> kmer_status {
+        MCHK(dalloc(&d, db->m));                     // (room for every candidate: the select writes what it finds)
+        MCHK(dalloc(&dn, 1));
+        rocprim::counting_iterator<uint32_t> iota(0);
+        MROC(db->tmp, rocprim::select(t, b, iota, d, dn, (size_t)db->m, HasTemplate{db->O, db->T, tmpl}, s));
+        unsigned long long got = 0;
+        MCHK(hipMemcpyAsync(&got, dn, 8, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        if (got != ul) return set_err(KMER_E_DEVICE, "kmer_db_template_kmers: the CSR and the template's entries differ");
+        MCHK(hipMemcpyAsync(idx, d, std::min(cap, ul) * 4, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        return KMER_OK;
+    };
+    const kmer_status st = body();
+    if (d) (void)hipFree(d);
+    if (dn) (void)hipFree(dn);
+    return st;
+}
+
+kmer_status kmer_db_template_name(const kmer_db *db, uint32_t tmpl, const char **name, uint32_t *len) {
+    if (!db || tmpl >= db->nt || !name || !len)
+        return set_err(KMER_E_BAD_PARAM, "kmer_db_template_name: bad argument");
+    *name = db->names.c_str() + db->name_off[tmpl];
+    *len = (uint32_t)(db->name_off[tmpl + 1] - db->name_off[tmpl]);
     return KMER_OK;
 }
 

@@ -195,6 +195,90 @@ class TemplateDB:
         self._open(keys, np.ascontiguousarray(starts, dtype=np.uint64))
         return self
 
+    @classmethod
+    def from_fasta(cls, counter, data_or_path, flags=0):
+        """The DB built on the device from FASTA genomes (kmer_db_open_fasta):
+        record r is template r, its k-mers the A/C/G/T keys of the record's own
+        Map under `counter`'s configuration (k, prefix, canonical or not; any
+        single-device Counter, before a session or after a finish).  data: a
+        bytes-like object, or a path (memory-mapped).  Template meta comes from
+        the DB: 'sequence' = the name up to the first whitespace, 'species' =
+        the rest, 'lengths' / 'ulength' from template_stats."""
+        import mmap
+        import os
+        h = ctypes.c_void_p()
+        if isinstance(data_or_path, (str, os.PathLike)):
+            with open(data_or_path, "rb") as f:
+                size = os.fstat(f.fileno()).st_size
+                if size:
+                    with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                        view = np.frombuffer(mm, dtype=np.uint8)
+                        st = LIB.kmer_db_open_fasta(counter.h, ctypes.c_void_p(view.ctypes.data), size, flags,
+                                                    ctypes.byref(h))
+                        del view
+                else:
+                    st = LIB.kmer_db_open_fasta(counter.h, None, 0, flags, ctypes.byref(h))
+        else:
+            buf = np.frombuffer(bytes(data_or_path), dtype=np.uint8)
+            st = LIB.kmer_db_open_fasta(counter.h, ctypes.c_void_p(buf.ctypes.data) if len(buf) else None, len(buf),
+                                        flags, ctypes.byref(h))
+        _check(st, "kmer_db_open_fasta")
+        return cls._from_handle(h, counter)
+
+    @classmethod
+    def from_fasta_device(cls, counter, ptr, nbytes, stream=0, flags=0):
+        """The same from FASTA bytes in device memory (kmer_db_open_fasta_device):
+        from a record start, any alignment; ordered after the work queued on
+        `stream`, complete on return."""
+        h = ctypes.c_void_p()
+        _check(LIB.kmer_db_open_fasta_device(counter.h, ctypes.c_void_p(ptr), nbytes, flags, ctypes.c_void_p(stream),
+                                             ctypes.byref(h)), "kmer_db_open_fasta_device")
+        return cls._from_handle(h, counter)
+
+    @classmethod
+    def _from_handle(cls, h, counter):
+        self = cls.__new__(cls)
+        self.handle, self.k = h, counter.k
+        self.device = counter.device
+        lengths, ulengths = self.template_stats()
+        self.templates = []
+        for t in range(len(lengths)):
+            name = self.template_name(t).decode("latin-1")
+            parts = name.split(None, 1)
+            self.templates.append({"sequence": parts[0] if parts else "", "species": parts[1] if len(parts) > 1 else "",
+                                   "lengths": int(lengths[t]), "ulength": int(ulengths[t])})
+        self.summary = default_summary(self.templates)
+        return self
+
+    def template_stats(self):
+        """(lengths, ulengths): numpy uint64 arrays, one entry per template
+        (kmer_db_template_stats)."""
+        nt = self.info()["templates"]
+        a, b = np.zeros(max(nt, 1), dtype=np.uint64), np.zeros(max(nt, 1), dtype=np.uint64)
+        pu = ctypes.POINTER(ctypes.c_uint64)
+        _check(LIB.kmer_db_template_stats(self.handle, 0, nt, a.ctypes.data_as(pu), b.ctypes.data_as(pu)),
+               "kmer_db_template_stats")
+        return a[:nt], b[:nt]
+
+    def template_kmers(self, t, cap=None):
+        """Template t's k-mers as ascending indices into the DB's distinct
+        k-mers (TemplateDB.kmers decodes them), a numpy uint32 array
+        (kmer_db_template_kmers).  cap: at most that many are returned."""
+        n = ctypes.c_uint64()
+        _check(LIB.kmer_db_template_kmers(self.handle, t, 0, None, ctypes.byref(n)), "kmer_db_template_kmers")
+        want = n.value if cap is None else min(cap, n.value)
+        out = np.zeros(max(want, 1), dtype=np.uint32)
+        _check(LIB.kmer_db_template_kmers(self.handle, t, want, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          ctypes.byref(n)), "kmer_db_template_kmers")
+        return out[:want]
+
+    def template_name(self, t):
+        """Template t's name as bytes: its FASTA header line without '>' (empty
+        for a headerless record and for a DB opened from k-mer lists)."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint32()
+        _check(LIB.kmer_db_template_name(self.handle, t, ctypes.byref(p), ctypes.byref(n)), "kmer_db_template_name")
+        return ctypes.string_at(p.value, n.value) if n.value else b""
+
     def _open(self, keys, starts):
         h = ctypes.c_void_p()
         _check(LIB.kmer_db_open(self.device, self.k, keys, int(starts[-1]),
