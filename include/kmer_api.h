@@ -349,6 +349,75 @@ kmer_status kmer_table_screen_device(kmer_ctx *ctx, const void *d_bytes, size_t 
                                      uint32_t flags, void *stream, const void **d_rows, uint64_t *n_reads);
 kmer_status kmer_table_screen(kmer_ctx *ctx, const uint8_t *bytes, size_t len, uint64_t min_count,
                               uint32_t flags, kmer_read_screen *rows, uint64_t cap, uint64_t *n_reads);
+/* Reads filtered by their screen (after a table finish, until the next reset):
+ * the screen above, then the records of the reads that pass a predicate on
+ * their rows, compacted on the device.  Input is FASTQ bytes under exactly the
+ * screen's rules (lines, reads, n_reads, line phase 0 in every call).
+ *   Records:  record r (0 <= r < n_reads) is the bytes from the start of line
+ *             4r up to and including the '\n' that ends line 4r + 3; when the
+ *             input has no such '\n' the record runs to the end of the input.
+ *             Records are back to back from offset 0.
+ *   consumed: the end of record n_reads - 1, or 0 when there is no read.
+ *   The tail: len - consumed bytes may remain -- an unfinished header line
+ *             after a complete record, or an input without any '\n'.  They
+ *             hold no read and are never part of the output; a streaming
+ *             caller carries them into the next call.
+ *   row(r):   the screen's row of read r at the call's min_count.
+ *   match(r): hits >= min_hits AND hits * frac_den >= frac_num * windows, in
+ *             exact (128-bit) arithmetic.  With min_hits = 0 and frac_num = 0
+ *             every read matches, also one without windows.
+ *   KMER_FILTER_PAIRED: records 2j and 2j + 1 are mates (interleaved pairs);
+ *             both get match(2j) OR match(2j + 1).  A last record without a
+ *             mate is judged alone.
+ *   keep(r):  match(r), negated under KMER_FILTER_DROP.
+ *   Output:   the kept records, verbatim and in input order, back to back.  No
+ *             byte is added: only the input's last record can lack its final
+ *             '\n', and it is then last in the output too.
+ *
+ * kmer_table_filter_device: the screen's preconditions and guarantees -- the
+ * bytes are in device memory, start at a record start and sit at any byte
+ * alignment; nothing outside [d_bytes, d_bytes + len) is loaded; the call
+ * waits for the work queued so far on `stream`, is complete on return, and a
+ * chunk in flight is settled first.  *d_out = out_len bytes, *d_keep = n_reads
+ * bytes of 0 / 1, *d_rows = the screen's n_reads rows: library-owned device
+ * memory, valid until the next screen, filter, reset or close.  The rows share
+ * the screen's buffer, so a filter ends the validity of an earlier screen's
+ * rows (and a screen that of a filter's three outputs).  Any of the three
+ * out-pointers may be NULL (NULL d_out: the records are not copied); one whose
+ * array is empty is set to NULL.  The extract's buffers stay valid.
+ * kmer_table_filter: host bytes; they go up in bounded pieces cut at record
+ * boundaries as in kmer_table_screen (under KMER_FILTER_PAIRED at pair
+ * boundaries, so mates are never split), and each piece's output and flags
+ * come down before the next piece goes up: device and pinned memory do not
+ * grow with len.  out == NULL with out_cap == 0 returns counts and flags only,
+ * and likewise keep; out_cap >= len always suffices, keep_cap >= n_reads is
+ * needed; a buffer that turns out too small is KMER_E_BAD_PARAM with a message
+ * naming both sizes (what was written before is unspecified).
+ *
+ * Checked before any device call: KMER_E_BAD_PARAM for a NULL context, p or
+ * res, NULL bytes with len > 0, frac_den == 0 or frac_num > frac_den, an
+ * unknown bit in flags, or the screen's own flag errors in screen_flags; len
+ * == 0 is KMER_OK with a zero result and touches nothing.  KMER_E_STATE,
+ * KMER_E_NONASCII, KMER_E_OOM and KMER_E_DEVICE exactly as in the screen: the
+ * table stays readable and the context usable.  The call leaves unchanged what
+ * the screen leaves unchanged. */
+enum { KMER_FILTER_DROP = 1u, KMER_FILTER_PAIRED = 2u };
+typedef struct {
+    uint64_t min_count;           /* the screen's */
+    uint64_t min_hits;
+    uint32_t frac_num, frac_den;  /* frac_den >= 1, frac_num <= frac_den */
+    uint32_t flags;               /* KMER_FILTER_* */
+    uint32_t screen_flags;        /* KMER_SCREEN_* of the underlying screen */
+} kmer_filter_params;             /* 32 bytes */
+typedef struct {
+    uint64_t n_reads, n_kept, out_len, consumed;
+} kmer_filter_result;
+kmer_status kmer_table_filter_device(kmer_ctx *ctx, const void *d_bytes, size_t len, const kmer_filter_params *p,
+                                     void *stream, const void **d_out, const void **d_keep, const void **d_rows,
+                                     kmer_filter_result *res);
+kmer_status kmer_table_filter(kmer_ctx *ctx, const uint8_t *bytes, size_t len, const kmer_filter_params *p,
+                              uint8_t *out, uint64_t out_cap, uint8_t *keep, uint64_t keep_cap,
+                              kmer_filter_result *res);
 /* The table read by value (after a table finish, until the next reset; the
  * calls may be repeated and interleaved with stats, digest, lookup and match,
  * and leave the table unchanged).  "The Map" is the Map this context's host

@@ -41,6 +41,10 @@ SCREEN_DIRECT = 1
 SCREEN_SORTED = 2
 SCREEN_PIECE_TEST = 4
 SCREEN_DIRECT_MAX = 16
+# kmer_table_filter* (include/kmer_api.h, KMER_FILTER_*): drop the matching reads instead of keeping
+# them; records 2j and 2j + 1 are mates and share one decision
+FILTER_DROP = 1
+FILTER_PAIRED = 2
 WRITE_JSON = 0      # JSON.stringify(mapToJSON(map)), lib/kmers.js:46-54
 WRITE_LEGACY = 1    # "{\nkey: count,...}\n", lib/index.js:381-388
 
@@ -56,6 +60,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
            "kmer_table_lookup", "kmer_table_lookup_device",
            "kmer_table_screen_device", "kmer_table_screen",
+           "kmer_table_filter_device", "kmer_table_filter",
            "kmer_table_spectrum", "kmer_table_extract_device", "kmer_table_extract",
            "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
@@ -87,6 +92,18 @@ class TableOverlap(ctypes.Structure):
 class ReadScreen(ctypes.Structure):
     """kmer_read_screen (kmer_table_screen): one row per read."""
     _fields_ = [(name, ctypes.c_uint64) for name in ("windows", "hits", "skipped", "sum")]
+
+
+class FilterParams(ctypes.Structure):
+    """kmer_filter_params (kmer_table_filter)."""
+    _fields_ = [("min_count", ctypes.c_uint64), ("min_hits", ctypes.c_uint64),
+                ("frac_num", ctypes.c_uint32), ("frac_den", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("screen_flags", ctypes.c_uint32)]
+
+
+class FilterResult(ctypes.Structure):
+    """kmer_filter_result (kmer_table_filter)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n_reads", "n_kept", "out_len", "consumed")]
 
 
 class Params(ctypes.Structure):
@@ -169,6 +186,11 @@ def _load():
                                                     ctypes.POINTER(vp), pu64]),
         "kmer_table_screen": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, u64, ctypes.c_uint32,
                                              ctypes.POINTER(ReadScreen), u64, pu64]),
+        "kmer_table_filter_device": (ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.POINTER(FilterParams), vp,
+                                                    ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                    ctypes.POINTER(FilterResult)]),
+        "kmer_table_filter": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(FilterParams),
+                                             vp, u64, vp, u64, ctypes.POINTER(FilterResult)]),
         "kmer_table_spectrum": (ctypes.c_int, [vp, ctypes.c_uint32, pu64, pu64]),
         "kmer_table_extract_device": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp), ctypes.POINTER(vp), pu64]),
         "kmer_table_extract": (ctypes.c_int, [vp, u64, u64, ctypes.POINTER(vp)]),
@@ -509,6 +531,40 @@ class Counter:
                                           out.ctypes.data_as(ctypes.POINTER(ReadScreen)), cap, ctypes.byref(n)),
                     "table_screen")
         return out[:n.value]
+
+    def table_filter_device(self, ptr: int, nbytes: int, min_count=1, min_hits=1, frac=(0, 1), flags=0,
+                            screen_flags=0, stream: int = 0):
+        """kmer_table_filter_device: FASTQ bytes in device memory (from a record
+        start, any alignment) screened against the table, and the records of
+        the reads with hits >= min_hits and hits / windows >= frac[0] / frac[1]
+        kept (FILTER_DROP: dropped; FILTER_PAIRED: mates 2j, 2j + 1 share one
+        decision) -> (d_out, d_keep, d_rows, result): result.out_len bytes of
+        kept records, result.n_reads keep flags (uint8 0 / 1) and the screen's
+        rows, in device memory the library owns (0 when empty) -- complete on
+        return, valid until the next screen, filter, reset or close."""
+        p = FilterParams(min_count, min_hits, frac[0], frac[1], flags, screen_flags)
+        out, keep, rows, res = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), FilterResult()
+        self._check(LIB.kmer_table_filter_device(self.h, ctypes.c_void_p(ptr), nbytes, ctypes.byref(p),
+                                                 ctypes.c_void_p(stream), ctypes.byref(out), ctypes.byref(keep),
+                                                 ctypes.byref(rows), ctypes.byref(res)), "table_filter_device")
+        return out.value or 0, keep.value or 0, rows.value or 0, res
+
+    def table_filter(self, data: bytes, min_count=1, min_hits=1, frac=(0, 1), flags=0, screen_flags=0):
+        """kmer_table_filter: FASTQ bytes on the host -> (bytes of the kept
+        records, keep as a numpy bool array with one entry per read, result);
+        data[result.consumed:] is the tail a streaming caller carries over."""
+        import numpy as np
+        data = bytes(data)
+        nl = data.count(b"\n")
+        cap = (nl - 1) // 4 + 1 if nl else 0
+        p = FilterParams(min_count, min_hits, frac[0], frac[1], flags, screen_flags)
+        out = np.empty(max(len(data), 1), dtype=np.uint8)
+        keep = np.zeros(max(cap, 1), dtype=np.uint8)
+        res = FilterResult()
+        self._check(LIB.kmer_table_filter(self.h, data, len(data), ctypes.byref(p), ctypes.c_void_p(out.ctypes.data),
+                                          len(data), ctypes.c_void_p(keep.ctypes.data), cap, ctypes.byref(res)),
+                    "table_filter")
+        return out[:res.out_len].tobytes(), keep[:res.n_reads].astype(bool), res
 
     def table_spectrum(self, nbins=256):
         """Table mode, after a finish: the abundance spectrum of the Map --

@@ -292,6 +292,10 @@ kmer_status kmer_close(kmer_ctx *c) {
     c->tsc_code.release();
     c->tsc_rows.release();
     c->tsc_in.release();
+    for (auto *b : {&c->tfl_rend, &c->tfl_seg_src, &c->tfl_seg_out}) b->release();
+    c->tfl_keep.release();
+    c->tfl_scan.release();
+    c->tfl_out.release();
     c->gm_keys.release();
     c->gm_keys2.release();
     for (auto *b : {&c->gm_cnt, &c->gm_cnt2, &c->gm_first, &c->gm_first2, &c->gm_h1, &c->gm_h2, &c->gm_h1b, &c->gm_h2b})
@@ -1088,6 +1092,27 @@ kmer_status kmer_table_screen_device(kmer_ctx *c, const void *d_bytes, size_t le
     return KMER_OK;
 }
 
+// The end of the host calls' next piece from pos: whole units of `unit` lines
+// (4: a record, 8: a pair of mates), as many as fit the batch, at least one;
+// the input's tail goes with the last piece.
+static uint64_t screen_piece_end(const uint8_t *bytes, uint64_t len, uint64_t pos, uint64_t batch, uint64_t unit) {
+    uint64_t e = pos, good = 0, cnt = 0;
+    bool more = false;
+    while (e < len) {
+        const void *nl = memchr(bytes + e, '\n', len - e);
+        if (!nl) break;
+        e = (uint64_t)((const uint8_t *)nl - bytes) + 1;
+        if ((++cnt % unit) != 0) continue;
+        if (e - pos <= batch || !good) good = e;
+        if (e - pos >= batch) {
+            more = true;
+            break;
+        }
+    }
+    if (!more && (len - pos <= batch || !good)) good = len;  // the input's tail
+    return good;
+}
+
 kmer_status kmer_table_screen(kmer_ctx *c, const uint8_t *bytes, size_t len, uint64_t min_count, uint32_t flags,
                               kmer_read_screen *rows, uint64_t cap, uint64_t *n_reads) {
     if (n_reads) *n_reads = 0;
@@ -1104,21 +1129,7 @@ kmer_status kmer_table_screen(kmer_ctx *c, const uint8_t *bytes, size_t len, uin
     const uint64_t batch = c->p.batch_bytes ? c->p.batch_bytes : SCREEN_BATCH;
     uint64_t done = 0;
     for (uint64_t pos = 0; pos < len;) {
-        // the piece: whole records (4 lines), as many as fit the batch, at least one
-        uint64_t e = pos, good = 0, cnt = 0;
-        bool more = false;
-        while (e < len) {
-            const void *nl = memchr(bytes + e, '\n', len - e);
-            if (!nl) break;
-            e = (uint64_t)((const uint8_t *)nl - bytes) + 1;
-            if ((++cnt & 3) != 0) continue;
-            if (e - pos <= batch || !good) good = e;
-            if (e - pos >= batch) {
-                more = true;
-                break;
-            }
-        }
-        if (!more && (len - pos <= batch || !good)) good = len;  // the input's tail
+        const uint64_t good = screen_piece_end(bytes, len, pos, batch, 4);
         const uint64_t m = good - pos;
         if (!screen_ensure(c->tsc_in, m, s)) return fail(c, KMER_E_OOM, "device allocation failed (read screen: input piece)");
         st = upload(c, c->tsc_in.p, bytes + pos, m, s);
@@ -1135,6 +1146,150 @@ kmer_status kmer_table_screen(kmer_ctx *c, const uint8_t *bytes, size_t len, uin
         pos = good;
     }
     if (done != n) return fail(c, KMER_E_DEVICE, "read screen: rows and reads differ");
+    return KMER_OK;
+}
+
+// ---- read filter (kmer_filter.hip) ----
+static_assert(sizeof(kmer_filter_params) == 32 && sizeof(kmer_filter_result) == 32, "kmer_filter_params / _result");
+static_assert(KMER_FILTER_DROP == FILTER_DROP && KMER_FILTER_PAIRED == FILTER_PAIRED, "KMER_FILTER_*: the mark kernel's bits");
+
+static bool filter_bad_params(const kmer_filter_params *p) {
+    return p->frac_den == 0 || p->frac_num > p->frac_den || (p->flags & ~(KMER_FILTER_DROP | KMER_FILTER_PAIRED)) ||
+           screen_bad_flags(p->screen_flags);
+}
+
+// The filter of len device-resident bytes that start at a record start: the
+// screen (c->tsc_rows), then c->tfl_keep and, if want_out, the kept records in
+// c->tfl_out; queued on the context's stream and waited for.
+static kmer_status filter_run(kmer_ctx *c, const uint8_t *d, uint64_t len, const kmer_filter_params *p, bool want_out,
+                              kmer_filter_result *res) {
+    hipStream_t s = c->stream;
+    memset(res, 0, sizeof(*res));
+    uint64_t n = 0;
+    kmer_status st = screen_run(c, d, len, p->min_count, p->screen_flags, &n);
+    if (st || !n) return st;
+    const uint64_t pad = ((len + 15) & ~15ull) + 16;
+    if (!screen_ensure(c->tfl_rend, n, s) || !screen_ensure(c->tfl_keep, n, s) || !screen_ensure(c->tfl_scan, n, s) ||
+        !screen_ensure(c->tfl_seg_src, n + 1, s) || !screen_ensure(c->tfl_seg_out, n + 1, s) ||
+        (want_out && !screen_ensure(c->tfl_out, pad, s)))
+        return fail(c, KMER_E_OOM, "device allocation failed (read filter: " + std::to_string(n) + " records, " +
+                                       std::to_string(len) + " bytes)");
+    FilterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.data = d;
+    a.len = len;
+    a.n_nl = c->cl_nl;
+    a.n_reads = n;
+    a.slots = c->cl_slots ? c->nlslots.p : nullptr;
+    a.tcount = c->tcount.p;
+    a.tbase = c->tbase.p;
+    a.n_tiles = (uint32_t)((len + TILE - 1) / TILE);
+    a.cap = NL_SLOTS;
+    a.nl = c->nlpos.p;
+    a.rows = c->tsc_rows.p;
+    a.min_hits = p->min_hits;
+    a.frac_num = p->frac_num;
+    a.frac_den = p->frac_den;
+    a.flags = p->flags;
+    a.rend = c->tfl_rend.p;
+    a.keep = c->tfl_keep.p;
+    a.scan = c->tfl_scan.p;
+    a.seg_src = c->tfl_seg_src.p;
+    a.seg_out = c->tfl_seg_out.p;
+    a.out = c->tfl_out.p;
+    HIPCHK(c, launch_filter_ends(a, s));
+    HIPCHK(c, launch_filter_mark(a, s));
+    ROCPRIM_RUN(c, rocprim::inclusive_scan(t, b, c->tfl_scan.p, c->tfl_scan.p, (size_t)n, FilterScanPlus(), s));
+    HIPCHK(c, launch_filter_segments(a, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_small + 18, c->tfl_scan.p + n - 1, sizeof(FilterScan), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_small + 21, c->tfl_rend.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    res->n_reads = n;
+    res->n_kept = c->h_small[18];
+    res->out_len = c->h_small[19];
+    res->consumed = c->h_small[21];
+    a.n_segs = c->h_small[20];
+    a.out_len = res->out_len;
+    if (res->n_kept > n || res->out_len > len || res->consumed > len || a.n_segs > res->n_kept)
+        return fail(c, KMER_E_DEVICE, "read filter: the kept records exceed the input");
+    if (want_out && a.out_len) {
+        HIPCHK(c, launch_filter_copy(a, (uint32_t)std::max(c->n_cu, 1), s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return KMER_OK;
+}
+
+kmer_status kmer_table_filter_device(kmer_ctx *c, const void *d_bytes, size_t len, const kmer_filter_params *p,
+                                     void *stream, const void **d_out, const void **d_keep, const void **d_rows,
+                                     kmer_filter_result *res) {
+    if (d_out) *d_out = nullptr;
+    if (d_keep) *d_keep = nullptr;
+    if (d_rows) *d_rows = nullptr;
+    if (res) memset(res, 0, sizeof(*res));
+    if (!c || !p || !res || (len && !d_bytes) || filter_bad_params(p)) return KMER_E_BAD_PARAM;
+    if (len == 0) return KMER_OK;
+    kmer_status st = screen_state(c);
+    if (st) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    HIPCHK(c, hipEventRecord(c->evw, (hipStream_t)stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evw, 0));
+    st = filter_run(c, (const uint8_t *)d_bytes, len, p, d_out != nullptr, res);
+    if (st) {
+        memset(res, 0, sizeof(*res));
+        return st;
+    }
+    if (d_out && res->out_len) *d_out = c->tfl_out.p;
+    if (d_keep && res->n_reads) *d_keep = c->tfl_keep.p;
+    if (d_rows && res->n_reads) *d_rows = c->tsc_rows.p;
+    return KMER_OK;
+}
+
+kmer_status kmer_table_filter(kmer_ctx *c, const uint8_t *bytes, size_t len, const kmer_filter_params *p, uint8_t *out,
+                              uint64_t out_cap, uint8_t *keep, uint64_t keep_cap, kmer_filter_result *res) {
+    if (res) memset(res, 0, sizeof(*res));
+    if (!c || !p || !res || (len && !bytes) || (out_cap && !out) || (keep_cap && !keep) || filter_bad_params(p))
+        return KMER_E_BAD_PARAM;
+    if (len == 0) return KMER_OK;
+    kmer_status st = screen_state(c);
+    if (st) return st;
+    const uint64_t n_nl = count_newlines(bytes, len);
+    const uint64_t n = n_nl ? (n_nl - 1) / 4 + 1 : 0;
+    if (keep && keep_cap < n)
+        return fail(c, KMER_E_BAD_PARAM, "read filter: " + std::to_string(n) + " records, room for " +
+                                             std::to_string(keep_cap) + " keep flags");
+    if (hipSetDevice(c->device) != hipSuccess) return KMER_E_DEVICE;
+    hipStream_t s = c->stream;
+    const uint64_t batch = c->p.batch_bytes ? c->p.batch_bytes : SCREEN_BATCH;
+    const uint64_t unit = (p->flags & KMER_FILTER_PAIRED) ? 8 : 4;   // lines per cut: a record, or a pair of mates
+    kmer_filter_result tot;
+    memset(&tot, 0, sizeof(tot));
+    for (uint64_t pos = 0; pos < len;) {
+        const uint64_t good = screen_piece_end(bytes, len, pos, batch, unit);
+        const uint64_t m = good - pos;
+        if (!screen_ensure(c->tsc_in, m, s)) return fail(c, KMER_E_OOM, "device allocation failed (read filter: input piece)");
+        st = upload(c, c->tsc_in.p, bytes + pos, m, s);
+        if (st) return st;
+        kmer_filter_result r;
+        st = filter_run(c, c->tsc_in.p, m, p, out != nullptr, &r);
+        if (st) return st;
+        if (tot.n_reads + r.n_reads > n) return fail(c, KMER_E_DEVICE, "read filter: more records than reads");
+        if (out && tot.out_len + r.out_len > out_cap)
+            return fail(c, KMER_E_BAD_PARAM, "read filter: the kept records need at least " +
+                                                 std::to_string(tot.out_len + r.out_len) + " bytes, room for " +
+                                                 std::to_string(out_cap));
+        if (keep && r.n_reads)
+            HIPCHK(c, hipMemcpyAsync(keep + tot.n_reads, c->tfl_keep.p, r.n_reads, hipMemcpyDeviceToHost, s));
+        if (out && r.out_len)
+            HIPCHK(c, hipMemcpyAsync(out + tot.out_len, c->tfl_out.p, r.out_len, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        tot.n_reads += r.n_reads;
+        tot.n_kept += r.n_kept;
+        tot.out_len += r.out_len;
+        tot.consumed = pos + r.consumed;
+        pos = good;
+    }
+    if (tot.n_reads != n) return fail(c, KMER_E_DEVICE, "read filter: records and reads differ");
+    *res = tot;
     return KMER_OK;
 }
 

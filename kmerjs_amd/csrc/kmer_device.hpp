@@ -1,7 +1,7 @@
 // kmer_device.hpp — device helpers shared by the kernel translation units
 // (kmer_kernels.hip, kmer_table.hip, kmer_dense.hip, kmer_fasta.hip,
 // kmer_lookup.hip, kmer_probe.hip, kmer_abundance.hip, kmer_setops.hip,
-// kmer_screen.hip, kmer_dbfasta.hip): one
+// kmer_screen.hip, kmer_filter.hip, kmer_dbfasta.hip): one
 // definition of each primitive that more than one kernel uses.  The
 // host/device contract (structs, constants, launch_* declarations) is
 // kmer_internal.hpp.

@@ -662,6 +662,8 @@ kmer_status chunk_lines(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t n_
     if (e & ERR_LINE_OVERFLOW)                   // (short lines: two passes; other bits kept)
         HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_err, (int)(e & ~ERR_LINE_OVERFLOW), 1, s));
     const uint64_t n_nl = c->h_small[14] + (uint32_t)c->h_small[15];
+    c->cl_slots = slots;
+    c->cl_nl = n_nl;
     if (!slots) {
         HIPCHK(c, c->nlpos.ensure(n_nl + 1, s));
         HIPCHK(c, launch_nl_write(d, len, n_tiles, c->tbase.p, c->nlpos.p, s));

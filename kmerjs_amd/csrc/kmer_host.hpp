@@ -151,6 +151,8 @@ struct kmer_ctx {
     DBuf<uint32_t> tcount;         // dense-hit path: '\n' per tile
     DBuf<uint64_t> tbase, nlpos;   // ... exclusive scan, chunk-relative '\n' positions (or sequence-line bounds)
     DBuf<uint16_t> nlslots;        // tile-relative '\n' positions, NL_SLOTS per tile
+    bool cl_slots = false;         // the last chunk_lines left the '\n' positions in nlslots (else: in nlpos)
+    uint64_t cl_nl = 0;            // ... and found this many '\n'
     uint64_t host_lines = 0;       // StreamPos.lines as last seen by the host (dense-hit path)
     DBuf<HitRec> hits, ovf;
     DBuf<uint64_t> hits_hi, ovf_hi;   // k > 32: the first k - 32 bases of each hit record's window
@@ -285,6 +287,11 @@ struct kmer_ctx {
     DBuf<uint32_t> tsc_bkt, tsc_bkt2, tsc_idx, tsc_idx2;
     DBuf<ScreenRow> tsc_rows;      // one row per read (valid until the next screen)
     DBuf<uint8_t> tsc_in;          // host call: one uploaded piece of the input
+    // read filter (kmer_filter.hip): record ends, keep flags, the scan, the kept runs, the output
+    DBuf<uint64_t> tfl_rend, tfl_seg_src, tfl_seg_out;
+    DBuf<uint8_t> tfl_keep;
+    DBuf<FilterScan> tfl_scan;
+    DBuf<uint8_t> tfl_out;         // the kept records (valid until the next screen or filter)
     uint32_t t_nq = TAB_NQ;        // buckets the last table finish owns (an exchanged table: its rank's share)
     DBuf<unsigned long long> tjoin;   // set operations (kmer_setops.hip): [0..7] compare's sums, [8] setop count / cursor
     uint64_t t_lines = 0;          // a group: the input lines of its last count (kmer_table_extract)

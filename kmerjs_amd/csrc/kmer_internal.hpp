@@ -923,6 +923,60 @@ hipError_t launch_screen_reduce(const TabScreen &a, hipStream_t s);
 hipError_t screen_sort_bytes(uint64_t m, size_t *bytes);
 hipError_t launch_screen_sort(uint32_t *bkt, uint32_t *bkt2, uint32_t *idx, uint32_t *idx2, uint64_t m, void *tmp,
                               size_t tmp_bytes, const uint32_t **sb, const uint32_t **si, hipStream_t s);
+// Read filter (kmer_filter.hip, kmer_table_filter): the records of the screened
+// reads that pass the predicate, compacted on the device.
+// a * b as a 96-bit number (hi: bits 64.., lo: bits 0..63), exact
+__host__ __device__ inline void filter_mul96(uint64_t a, uint32_t b, uint64_t *hi, uint64_t *lo) {
+    const uint64_t l = (a & 0xFFFFFFFFull) * b;
+    const uint64_t h = (a >> 32) * b + (l >> 32);
+    *lo = (h << 32) | (l & 0xFFFFFFFFull);
+    *hi = h >> 32;
+}
+// match(r): hits >= min_hits AND hits * frac_den >= frac_num * windows, the
+// products in exact arithmetic (kmer_api.h, kmer_filter_params)
+__host__ __device__ inline bool filter_match(uint64_t hits, uint64_t windows, uint64_t min_hits, uint32_t frac_num,
+                                             uint32_t frac_den) {
+    if (hits < min_hits) return false;
+    uint64_t lh, ll, rh, rl;
+    filter_mul96(hits, frac_den, &lh, &ll);
+    filter_mul96(windows, frac_num, &rh, &rl);
+    return lh > rh || (lh == rh && ll >= rl);
+}
+constexpr uint32_t FILTER_DROP = 1u, FILTER_PAIRED = 2u;   // (KMER_FILTER_*)
+constexpr uint32_t FL_TILE = 4096;                     // output bytes per workgroup tile of the copy: 256 lanes x 16
+constexpr uint32_t FL_SEGS = FL_TILE / 4 + 2;          // segment bounds a tile can hold (a record is >= 4 bytes), + the end
+struct FilterScan {                                    // per record, then its inclusive scan
+    uint64_t kept, bytes, segs;                        // kept records, their bytes, kept runs begun
+};
+struct FilterScanPlus {
+    __host__ __device__ FilterScan operator()(const FilterScan &x, const FilterScan &y) const {
+        return FilterScan{x.kept + y.kept, x.bytes + y.bytes, x.segs + y.segs};
+    }
+};
+struct FilterArgs {
+    const uint8_t *data;           // the input: nothing outside [data, data + len) is loaded
+    uint64_t len;
+    uint64_t n_nl, n_reads;        // '\n' of the input, records
+    // the '\n' positions as chunk_lines left them: per-tile slots, or nl (flat) when slots is null
+    const uint16_t *slots;
+    const uint32_t *tcount;
+    const uint64_t *tbase;
+    uint32_t n_tiles, cap;
+    const uint64_t *nl;
+    const ScreenRow *rows;         // by read
+    uint64_t min_hits;
+    uint32_t frac_num, frac_den, flags;
+    uint64_t *rend;                // by record: its end (the start of the next one)
+    uint8_t *keep;                 // by record: 0 / 1
+    FilterScan *scan;              // by record
+    uint64_t *seg_src, *seg_out;   // by kept run: where it begins in the input / in the output; seg_out[n_segs] = out_len
+    uint64_t n_segs, out_len;      // (the copy)
+    uint8_t *out;                  // 16-byte aligned, room for out_len rounded up to 16
+};
+hipError_t launch_filter_ends(const FilterArgs &a, hipStream_t s);
+hipError_t launch_filter_mark(const FilterArgs &a, hipStream_t s);
+hipError_t launch_filter_segments(const FilterArgs &a, hipStream_t s);
+hipError_t launch_filter_copy(const FilterArgs &a, uint32_t n_cu, hipStream_t s);
 // Template DB from FASTA (kmer_dbfasta.hip, kmer_db_open_fasta): every forward
 // window w of every record's joined sequence gives the A/C/G/T keys of "the
 // record's own Map" as the matcher's 2-bit codes.  The keys of a window, from
