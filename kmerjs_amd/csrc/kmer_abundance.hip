@@ -5,13 +5,14 @@
 // kmer_probe.hip.
 //
 // One walk serves all three kernels (tab_abund_kernel<MODE>).  A wave takes 64
-// consecutive buckets, lane i bucket 64 g + i, and reads its extent (start[q],
-// nd[q]).  A short bucket (<= AB_LANE_MAX entries, every bucket of a small
-// table) is walked by its own lane; the longer ones by the whole wave, one
-// after the other: all 64 lanes stream the bucket strided, AB_UNROLL 512-byte
-// wave loads in flight per round.  Every cross-lane read (ballot, readlane,
-// shuffle, DPP scan) sits at the wave-uniform level of the loops, outside the
-// per-lane branches; the loops over a bucket have wave-uniform trip counts.
+// consecutive buckets, lane i bucket 64 g + i, and reads its extent
+// (kmer_device.hpp: tab_extent).  A short bucket (<= TAB_LANE_MAX entries, every
+// bucket of a small table) is walked by its own lane; the longer ones by the
+// whole wave, one after the other: all 64 lanes stream the bucket strided,
+// TAB_UNROLL 512-byte wave loads in flight per round.  Every cross-lane read
+// (ballot, readlane, shuffle, DPP scan) sits at the wave-uniform level of the
+// loops, outside the per-lane branches; the loops over a bucket have
+// wave-uniform trip counts.
 //
 //   spectrum  value v of an entry, weight w = its Map keys (0, 1 or 2):
 //             v <= AB_REGS          per-lane registers, wave-reduced at the end
@@ -37,8 +38,6 @@
 
 namespace kmerhip {
 
-constexpr uint32_t AB_LANE_MAX = 16;     // bucket entries up to which the bucket's own lane walks it
-constexpr uint32_t AB_UNROLL = 8;        // wave loads (64 entries, 512 B each) in flight per round of a wave walk
 constexpr uint32_t AB_FLUSH = 1u << 29;  // weight a wave adds before it moves the LDS bins out
 constexpr uint32_t AB_GROUPS = TAB_NQ / 64;
 enum { AB_SPECTRUM = 0, AB_COUNT = 1, AB_WRITE = 2 };
@@ -79,25 +78,10 @@ __device__ __forceinline__ void ab_flush(const TabAbund &a, uint32_t *bins, uint
 // extract: an entry's Map keys (planar codes) and value; 0 keys when the value is out of range
 __device__ __forceinline__ uint32_t ab_ext_entry(const TabAbund &a, uint64_t e, uint32_t q, uint64_t keys[2], uint64_t *v) {
     const uint64_t h = ((uint64_t)q << TAB_RBITS) | (e >> 20);
-    uint64_t c = e & TAB_CMAX;
-    if (c == TAB_CMAX) {                                         // the count is in the big list (tiny: linear)
-        c = 0;
-        for (uint64_t t = 0; t < a.n_big; ++t)
-            if (a.big[t].h == h) c = a.big[t].count;
-    }
     bool dbl;
     const uint32_t n = tab_entry_keys(h, a.k, a.plo, a.phi, a.pmask, a.canonical != 0, keys, &dbl);
-    *v = dbl ? 2 * c : c;
+    *v = tab_value(a.big, a.n_big, true, e, h, dbl);
     return *v >= a.lo && *v <= a.hi ? n : 0u;
-}
-
-// write: t slots for this lane, one returning atomic for the wave (wave-uniform call)
-__device__ __forceinline__ uint64_t ab_reserve(unsigned long long *cursor, uint32_t t, uint32_t lane) {
-    const uint32_t incl = wave_incl_sum(t);
-    const uint32_t total = readlane32(incl, 63);
-    uint64_t base = 0;
-    if (total && lane == 0) base = atomicAdd(cursor, (unsigned long long)total);
-    return readlane64(base, 0) + (incl - t);
 }
 
 __device__ __forceinline__ void ab_put(const TabAbund &a, uint64_t slot, uint64_t key, uint64_t v) {
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(256) void tab_abund_kernel(const TabAbund a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t table_end = a.start[TAB_NQ] < a.cap ? a.start[TAB_NQ] : a.cap;
+    const uint64_t table_end = tab_end(a);
     const uint32_t w0 = a.canonical ? 1u : 2u;                   // (no decode: every entry is w0 Map keys)
     if (MODE == AB_SPECTRUM) {
         for (uint32_t i = threadIdx.x; i < AB_LDS_BINS; i += blockDim.x) bins[i] = 0;
@@ -128,22 +112,12 @@ __global__ __launch_bounds__(256) void tab_abund_kernel(const TabAbund a) {
     uint32_t seen = 0;                                           // spectrum: weight since the wave's last flush (a bound)
     for (uint32_t g = wave; g < AB_GROUPS; g += nwaves) {        // (wave-uniform)
         const uint32_t q = (g << 6) + lane;
-        const uint32_t L = a.nd[q];
-        uint64_t base = 0;
-        uint32_t len = 0;
-        if (L) {
-            base = a.start[q];
-            if (base > table_end || L > table_end - base) {      // an extent past the table is not read
-                atomicOr(a.err, ERR_TAB_LOOKUP);
-                *a.badq = q;
-            } else {
-                len = L;
-            }
-        }
-        const uint32_t own = len <= AB_LANE_MAX ? len : 0u;      // lane-per-bucket: no cross-lane reads inside
+        uint64_t base;
+        const uint32_t len = tab_extent(a, table_end, q, base);
+        const uint32_t own = len <= TAB_LANE_MAX ? len : 0u;      // lane-per-bucket: no cross-lane reads inside
         if (MODE == AB_SPECTRUM) {
             for (uint32_t j = 0; j < own; ++j) ab_spec_entry<DECODE>(a, a.ent[base + j], q, w0, r, bins);
-            seen += 64 * AB_LANE_MAX * 2;
+            seen += 64 * TAB_LANE_MAX * 2;
             if (seen >= AB_FLUSH) {                              // (wave-uniform)
                 ab_flush(a, bins, lane);
                 seen = 0;
@@ -159,52 +133,52 @@ __global__ __launch_bounds__(256) void tab_abund_kernel(const TabAbund a) {
                 uint64_t keys[2], v;
                 t += ab_ext_entry(a, a.ent[base + j], q, keys, &v);
             }
-            uint64_t slot = ab_reserve(a.n_out, t, lane);
+            uint64_t slot = wave_reserve(a.n_out, t, lane);
             for (uint32_t j = 0; j < own; ++j) {
                 uint64_t keys[2], v;
                 const uint32_t n = ab_ext_entry(a, a.ent[base + j], q, keys, &v);
                 for (uint32_t i = 0; i < n; ++i) ab_put(a, slot++, keys[i], v);
             }
         }
-        uint64_t todo = __ballot(len > AB_LANE_MAX);             // buckets the wave walks together
+        uint64_t todo = __ballot(len > TAB_LANE_MAX);             // buckets the wave walks together
         while (todo) {                                           // (wave-uniform)
             const uint32_t j = (uint32_t)__builtin_ctzll(todo);
             todo &= todo - 1;
             const uint64_t b = readlane64(base, j);
             const uint64_t Lj = readlane32(len, j);
             const uint32_t qj = (g << 6) + j;
-            for (uint64_t o = 0; o < Lj; o += 64 * AB_UNROLL) {  // (wave-uniform trip count)
-                uint64_t e[AB_UNROLL];
+            for (uint64_t o = 0; o < Lj; o += 64 * TAB_UNROLL) {  // (wave-uniform trip count)
+                uint64_t e[TAB_UNROLL];
 #pragma unroll
-                for (uint32_t u = 0; u < AB_UNROLL; ++u) {
+                for (uint32_t u = 0; u < TAB_UNROLL; ++u) {
                     const uint64_t p = o + u * 64 + lane;
                     e[u] = p < Lj ? a.ent[b + p] : 0;
                 }
                 if (MODE == AB_SPECTRUM) {
 #pragma unroll
-                    for (uint32_t u = 0; u < AB_UNROLL; ++u)
+                    for (uint32_t u = 0; u < TAB_UNROLL; ++u)
                         if (o + u * 64 + lane < Lj) ab_spec_entry<DECODE>(a, e[u], qj, w0, r, bins);
-                    seen += 64 * AB_UNROLL * 2;
+                    seen += 64 * TAB_UNROLL * 2;
                     if (seen >= AB_FLUSH) {                      // (wave-uniform) before a bin can wrap
                         ab_flush(a, bins, lane);
                         seen = 0;
                     }
                 } else if (MODE == AB_COUNT) {
 #pragma unroll
-                    for (uint32_t u = 0; u < AB_UNROLL; ++u) {
+                    for (uint32_t u = 0; u < TAB_UNROLL; ++u) {
                         uint64_t keys[2], v;
                         if (o + u * 64 + lane < Lj) mine += ab_ext_entry(a, e[u], qj, keys, &v);
                     }
                 } else {
                     uint32_t t = 0;
 #pragma unroll
-                    for (uint32_t u = 0; u < AB_UNROLL; ++u) {
+                    for (uint32_t u = 0; u < TAB_UNROLL; ++u) {
                         uint64_t keys[2], v;
                         if (o + u * 64 + lane < Lj) t += ab_ext_entry(a, e[u], qj, keys, &v);
                     }
-                    uint64_t slot = ab_reserve(a.n_out, t, lane);
+                    uint64_t slot = wave_reserve(a.n_out, t, lane);
 #pragma unroll
-                    for (uint32_t u = 0; u < AB_UNROLL; ++u) {
+                    for (uint32_t u = 0; u < TAB_UNROLL; ++u) {
                         uint64_t keys[2], v;
                         if (o + u * 64 + lane < Lj) {
                             const uint32_t n = ab_ext_entry(a, e[u], qj, keys, &v);
@@ -218,8 +192,7 @@ __global__ __launch_bounds__(256) void tab_abund_kernel(const TabAbund a) {
     if (MODE == AB_SPECTRUM) {
 #pragma unroll
         for (uint32_t i = 0; i < AB_REGS; ++i) {
-            uint64_t x = r[i];
-            for (int d = 32; d >= 1; d >>= 1) x += (uint64_t)__shfl_xor((long long)x, d);
+            const uint64_t x = wave_sum(r[i]);
             if (lane == 0 && x) atomicAdd(&a.hist[i + 1], (unsigned long long)x);
         }
         __syncthreads();                                         // every wave's LDS adds are in
@@ -228,7 +201,7 @@ __global__ __launch_bounds__(256) void tab_abund_kernel(const TabAbund a) {
             if (x) atomicAdd(&a.hist[i], (unsigned long long)x);
         }
     } else if (MODE == AB_COUNT) {
-        for (int d = 32; d >= 1; d >>= 1) mine += (uint64_t)__shfl_xor((long long)mine, d);
+        mine = wave_sum(mine);
         if (lane == 0 && mine) atomicAdd(a.n_out, (unsigned long long)mine);
     }
 }
@@ -243,10 +216,8 @@ __global__ __launch_bounds__(256) void tab_spectrum_tail_kernel(const unsigned l
         n += x;
         s += x * v;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        n += (uint64_t)__shfl_xor((long long)n, d);
-        s += (uint64_t)__shfl_xor((long long)s, d);
-    }
+    n = wave_sum(n);
+    s = wave_sum(s);
     if (lane == 0 && n) {
         atomicAdd(&out[0], (unsigned long long)n);
         atomicAdd(&out[1], (unsigned long long)s);

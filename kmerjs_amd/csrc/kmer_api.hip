@@ -1015,7 +1015,7 @@ static kmer_status screen_run(kmer_ctx *c, const uint8_t *d, uint64_t len, uint6
     size_t tmp_bytes = 0;
     bool ok = screen_ensure(c->tsc_h, cap, s) && screen_ensure(c->tsc_val, cap, s) && screen_ensure(c->tsc_code, cap, s);
     if (ok && sorted) {
-        HIPCHK(c, screen_sort_bytes(cap, &tmp_bytes));
+        HIPCHK(c, bucket_sort_bytes(cap, &tmp_bytes));
         for (auto *b : {&c->tsc_bkt, &c->tsc_bkt2, &c->tsc_idx, &c->tsc_idx2}) ok = ok && screen_ensure(*b, cap, s);
         ok = ok && screen_ensure(c->tmp, tmp_bytes + 16, s);
     }
@@ -1033,7 +1033,7 @@ static kmer_status screen_run(kmer_ctx *c, const uint8_t *d, uint64_t len, uint6
     a.len = len;
     a.lines = c->lines.p;
     a.wbase2 = c->wbase.p;
-    a.n_reads = n_seq;
+    a.n = n_seq;
     a.total = total;
     a.h = c->tsc_h.p;
     a.code = c->tsc_code.p;
@@ -1050,7 +1050,7 @@ static kmer_status screen_run(kmer_ctx *c, const uint8_t *d, uint64_t len, uint6
             HIPCHK(c, hipMemsetAsync(a.val, 0, a.m * 8, s));
         } else if (sorted) {
             const uint32_t *sb = nullptr, *si = nullptr;
-            HIPCHK(c, launch_screen_sort(c->tsc_bkt.p, c->tsc_bkt2.p, c->tsc_idx.p, c->tsc_idx2.p, a.m, c->tmp.p,
+            HIPCHK(c, launch_bucket_sort(c->tsc_bkt.p, c->tsc_bkt2.p, c->tsc_idx.p, c->tsc_idx2.p, a.m, c->tmp.p,
                                          tmp_bytes, &sb, &si, s));
             HIPCHK(c, launch_screen_probe(a, sb, si, cus, s));
         } else {

@@ -10,12 +10,9 @@
 //   lines    chunk_lines from line phase 0 without a length limit: one SeqLine
 //            and window count per record; their exclusive scan numbers the
 //            windows of all records in input order
-//   keys     dbf_keys_kernel, the shape of screen_keys_kernel (kmer_screen.hip):
-//            a lane takes DBF_NS consecutive windows, finds their record by a
-//            binary search in the window bases, loads the bytes they span as
-//            aligned dwords (the edge dwords patched byte by byte: no read
-//            outside the buffer), forms the bit planes and evaluates every
-//            window by shifts (dbf_window_keys).  Two passes over the same
+//   keys     dbf_keys_kernel: a lane takes WALK_NS consecutive windows
+//            (kmer_device.hpp: walk_windows, as the screen's keys kernel does)
+//            and evaluates each (dbf_window_keys).  Two passes over the same
 //            code: COUNT the keys of each lane -> exclusive scan -> WRITE the
 //            (2-bit code, template) pairs at the scanned offsets.  The pairs
 //            come out in window order, so template-major: what the stable
@@ -33,106 +30,39 @@ namespace kmerhip {
 
 namespace {
 
-// index of record r's first window (r == n_rec: the total)
-__device__ __forceinline__ uint64_t dbf_wb(const DbFasta &a, uint64_t r) {
-    return r < a.n_rec ? a.wbase2[r] >> 1 : a.total;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(256) void dbf_keys_kernel(const DbFasta a) {
     const uint32_t k = a.k;
-    const uint32_t kmask = k >= 32 ? ~0u : ((1u << k) - 1u);
-    const uint8_t *const end = a.data + a.len;
-    const uint64_t ngroups = (a.m + DBF_NS - 1) / DBF_NS;
+    const uint64_t ngroups = (a.m + WALK_NS - 1) / WALK_NS;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t i = g * DBF_NS;                                 // window of the piece
-        const uint64_t iend = i + DBF_NS < a.m ? i + DBF_NS : a.m;
-        uint64_t p = a.p0 + i;                                   // ... of the input
         uint32_t n = 0;                                          // keys of this lane's windows so far
         uint64_t o = 0;
         if (WRITE) o = a.off[g];
-        // the record of window p: the last r with wbase[r] <= p (records
-        // without windows share their successor's base and are passed over)
-        uint64_t lo = 0, hi = a.n_rec;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (dbf_wb(a, mid) <= p) lo = mid + 1;
-            else hi = mid;
-        }
-        uint64_t r = lo ? lo - 1 : 0;
-        while (i < iend && r < a.n_rec) {
-            const uint64_t b = dbf_wb(a, r), e = dbf_wb(a, r + 1);
-            if (e <= p) {                                        // (a record without windows)
-                ++r;
-                continue;
-            }
-            const uint64_t w0 = p - b;
-            const uint32_t nv = (uint32_t)(e - p < iend - i ? e - p : iend - i);   // 1 .. DBF_NS
-            // planes of the bytes [st + w0, st + w0 + nv + k - 1), from aligned dwords
-            const uint8_t *src = a.data + a.lines[r].start + w0;
-            const uint32_t off = (uint32_t)((uintptr_t)src & 3u);
-            const uint8_t *q0 = src - off;
-            const uint32_t span = off + nv + k - 1;              // (<= 3 + 16 + 31)
-            uint64_t LO = 0, HI = 0, EX = 0;
-            constexpr int NDW = (DBF_NS + 31 + 3 + 3) / 4;
-#pragma unroll
-            for (int d = 0; d < NDW; ++d) {
-                uint32_t x = 0x41414141u;                        // ('A': outside the windows, never looked at)
-                const uint8_t *q = q0 + 4 * d;
-                if ((uint32_t)(4 * d) < span && q < end) {
-                    if (q >= a.data && q + 4 <= end) {
-                        x = *(const uint32_t *)q;
-                    } else {                                     // the buffer's first / last dword: no read outside it
-                        for (int j = 0; j < 4; ++j)
-                            if (q + j >= a.data && q + j < end)
-                                x = (x & ~(0xFFu << (8 * j))) | ((uint32_t)q[j] << (8 * j));
+        walk_windows(a, k, g, [&](uint64_t, uint64_t r, uint64_t LO, uint64_t HI, uint32_t m, bool acgt) {
+            if (!acgt) return;                                   // a byte outside A/C/G/T: a record key, not in the DB
+            uint64_t cf, cr, keys[2];
+            screen_window_codes(LO, HI, m, k, &cf, &cr);
+            if (!WRITE) {
+                bool dbl;
+                n += screen_weight(cf, cr, k, a.plo, a.phi, a.pmask, a.canonical != 0, &dbl);
+            } else {
+                const uint32_t c = dbf_window_keys(cf, cr, k, a.plo, a.phi, a.pmask, a.canonical != 0, keys);
+                for (uint32_t j = 0; j < c; ++j) {
+                    if (o + n < a.n_pairs) {                     // (the counted slots: the two passes agree)
+                        a.codes[o + n] = keys[j];
+                        a.tmpl[o + n] = a.t0 + (uint32_t)r;
                     }
-                }
-                const uint32_t lo4 = __builtin_amdgcn_udot4((x ^ (x >> 1)) & 0x02020202u, 0x08040201u, 0u, false) >> 1;
-                const uint32_t hi4 = __builtin_amdgcn_udot4(x & 0x04040404u, 0x08040201u, 0u, false) >> 2;
-                const uint32_t cc = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
-                const uint32_t ne = __builtin_amdgcn_perm(0u, 0x54474341u, cc) ^ x;      // 0 where the byte is A/C/G/T
-                const uint32_t nz = (((ne & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | ne) & 0x80808080u;
-                const uint32_t ex4 = __builtin_amdgcn_udot4(nz >> 7, 0x08040201u, 0u, false);
-                LO |= (uint64_t)lo4 << (4 * d);
-                HI |= (uint64_t)hi4 << (4 * d);
-                EX |= (uint64_t)ex4 << (4 * d);
-            }
-            LO >>= off;
-            HI >>= off;
-            EX >>= off;
-            const uint32_t t = a.t0 + (uint32_t)r;
-#pragma unroll
-            for (uint32_t m = 0; m < DBF_NS; ++m) {
-                if (m >= nv) continue;
-                if ((uint32_t)(EX >> m) & kmask) continue;       // a byte outside A/C/G/T: a record key, not in the DB
-                uint64_t cf, cr, keys[2];
-                screen_window_codes(LO, HI, m, k, &cf, &cr);
-                if (!WRITE) {
-                    bool dbl;
-                    n += screen_weight(cf, cr, k, a.plo, a.phi, a.pmask, a.canonical != 0, &dbl);
-                } else {
-                    const uint32_t c = dbf_window_keys(cf, cr, k, a.plo, a.phi, a.pmask, a.canonical != 0, keys);
-                    for (uint32_t j = 0; j < c; ++j) {
-                        if (o + n < a.n_pairs) {                 // (the counted slots: the two passes agree)
-                            a.codes[o + n] = keys[j];
-                            a.tmpl[o + n] = t;
-                        }
-                        ++n;
-                    }
+                    ++n;
                 }
             }
-            i += nv;
-            p += nv;
-            ++r;
-        }
+        });
         if (!WRITE) a.cnt[g] = n;
     }
 }
 
 // lengths[r] += the pairs of the piece whose template is t0 + r
 __global__ __launch_bounds__(256) void dbf_lengths_kernel(const DbFasta a) {
-    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_rec; r += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t t = a.t0 + (uint32_t)r;
         uint64_t lo = 0, hi = a.n_pairs;
         while (lo < hi) {                                        // first pair of a template >= t
@@ -190,7 +120,7 @@ uint32_t dbf_grid(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<
 
 hipError_t launch_dbf_keys(const DbFasta &a, bool write, uint32_t n_cu, hipStream_t s) {
     if (a.m == 0) return hipSuccess;
-    const uint64_t groups = (a.m + DBF_NS - 1) / DBF_NS;
+    const uint64_t groups = (a.m + WALK_NS - 1) / WALK_NS;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((groups + 255) / 256, (uint64_t)std::max(n_cu, 1u) * 16);
     if (write) hipLaunchKernelGGL(dbf_keys_kernel<true>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(dbf_keys_kernel<false>, dim3(grid), dim3(256), 0, s, a);
@@ -198,8 +128,8 @@ hipError_t launch_dbf_keys(const DbFasta &a, bool write, uint32_t n_cu, hipStrea
 }
 
 hipError_t launch_dbf_lengths(const DbFasta &a, hipStream_t s) {
-    if (a.n_rec == 0 || a.n_pairs == 0) return hipSuccess;
-    hipLaunchKernelGGL(dbf_lengths_kernel, dim3(dbf_grid(a.n_rec)), dim3(256), 0, s, a);
+    if (a.n == 0 || a.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(dbf_lengths_kernel, dim3(dbf_grid(a.n)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -322,7 +252,7 @@ kmer_status dbf_piece(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t flag
     a.len = rlen;
     a.lines = c->lines.p;
     a.wbase2 = c->wbase.p;
-    a.n_rec = n_seq;
+    a.n = n_seq;
     a.total = total;
     a.k = c->p.k;
     for (size_t i = 0; i < c->prefix.size(); ++i) {  // (the planes of view_key_params, kmer_api.hip)
@@ -342,7 +272,7 @@ kmer_status dbf_piece(kmer_ctx *c, const uint8_t *d, uint64_t len, uint32_t flag
     for (uint64_t p0 = 0; possible && p0 < total; p0 += piece) {
         a.p0 = p0;
         a.m = std::min(piece, total - p0);
-        const uint64_t groups = (a.m + DBF_NS - 1) / DBF_NS;
+        const uint64_t groups = (a.m + WALK_NS - 1) / WALK_NS;
         DBF_ENSURE(c, B.cnt, groups);
         DBF_ENSURE(c, B.off, groups);
         a.cnt = B.cnt.p;

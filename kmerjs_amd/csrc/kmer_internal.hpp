@@ -850,15 +850,33 @@ struct TabProbe : TabView {
     const uint64_t *U, *O;
     uint64_t m;
     uint32_t *bkt, *bkt2, *idx, *idx2;   // scratch, m each: the probes' buckets and DB indices, sorted by bucket
-    void *tmp;                           // scratch of the sort (tab_probe_temp_bytes)
+    void *tmp;                           // scratch of the sort (bucket_sort_bytes)
     size_t tmp_bytes;
     uint32_t *qidx;
     uint64_t *hc;
     uint32_t *present;
     uint64_t *cnt;
 };
-hipError_t tab_probe_temp_bytes(uint64_t m, size_t *bytes);
 hipError_t launch_tab_probe(const TabProbe &a, uint32_t n_cu, hipStream_t s);
+// The sort of m (bucket or TAB_NQ: no probe, index) pairs by bucket that the
+// probe and the screen's sorted route share (kmer_probe.hip): one radix sort
+// over TAB_QBITS bits; *sb / *si: where the sorted pairs are
+constexpr uint32_t TAB_QBITS = TAB_L1 + TAB_L2 + 1;
+hipError_t bucket_sort_bytes(uint64_t m, size_t *bytes);
+hipError_t launch_bucket_sort(uint32_t *bkt, uint32_t *bkt2, uint32_t *idx, uint32_t *idx2, uint64_t m, void *tmp,
+                              size_t tmp_bytes, const uint32_t **sb, const uint32_t **si, hipStream_t s);
+// The windows of all lines (reads, records) of an input numbered in input
+// order and worked in pieces of consecutive windows, WALK_NS per lane
+// (kmer_device.hpp: walk_windows); a piece may end inside a line
+constexpr uint32_t WALK_NS = 16;                       // consecutive windows per lane
+struct WinWalk {
+    const uint8_t *data;           // the input: nothing outside [data, data + len) is loaded
+    uint64_t len;
+    const SeqLine *lines;          // by line (len 0: no windows)
+    const uint64_t *wbase2;        // by line: twice the index of its first window (scan of 2W)
+    uint64_t n, total;             // lines, windows of all lines
+    uint64_t p0, m;                // the piece: windows [p0, p0 + m)
+};
 // Read screen against a finished table (kmer_screen.hip, kmer_table_screen):
 // every forward window w of every read is one probe, by its class {w, rc w}.
 // The weight of a window is the value its read's own Map gives the class's
@@ -894,20 +912,12 @@ __host__ __device__ inline void screen_window_codes(uint64_t LO, uint64_t HI, ui
 // the one-byte code of a window: its weight (0, 1, 2), SC_DBL when the table's
 // count is doubled, or SC_SKIP (a byte outside A/C/G/T: a record key, not matched)
 constexpr uint8_t SC_WMASK = 3, SC_DBL = 4, SC_SKIP = 0x80;
-constexpr uint32_t SC_NS = 16;                         // consecutive windows per lane of the keys kernel
-constexpr uint32_t SC_BITS = TAB_L1 + TAB_L2 + 1;      // sort key: the bucket, or TAB_NQ (no probe)
 constexpr uint64_t SC_PIECE = 1ull << 26;              // windows per piece
 constexpr uint64_t SC_PIECE_TEST = 4096;               // ... with KMER_SCREEN_PIECE_TEST
 struct ScreenRow {                                     // (kmer_read_screen)
     uint64_t windows, hits, skipped, sum;
 };
-struct TabScreen : TabView {
-    const uint8_t *data;           // the input: nothing outside [data, data + len) is loaded
-    uint64_t len;
-    const SeqLine *lines;          // by read (len 0: no windows)
-    const uint64_t *wbase2;        // by read: twice the index of its first window (scan of 2W)
-    uint64_t n_reads, total;       // reads, windows of all reads
-    uint64_t p0, m;                // the piece: windows [p0, p0 + m)
+struct TabScreen : TabView, WinWalk {                  // (the lines are the reads)
     uint64_t *h;                   // by window of the piece: tab_key_h of its class
     uint8_t *code;                 // ... its code (SC_*)
     uint64_t *val;                 // ... the Map value of its class (0: absent or no probe)
@@ -920,9 +930,6 @@ hipError_t launch_screen_keys(const TabScreen &a, uint32_t n_cu, hipStream_t s);
 hipError_t launch_screen_probe(const TabScreen &a, const uint32_t *sb, const uint32_t *si, uint32_t n_cu,
                                hipStream_t s);
 hipError_t launch_screen_reduce(const TabScreen &a, hipStream_t s);
-hipError_t screen_sort_bytes(uint64_t m, size_t *bytes);
-hipError_t launch_screen_sort(uint32_t *bkt, uint32_t *bkt2, uint32_t *idx, uint32_t *idx2, uint64_t m, void *tmp,
-                              size_t tmp_bytes, const uint32_t **sb, const uint32_t **si, hipStream_t s);
 // Read filter (kmer_filter.hip, kmer_table_filter): the records of the screened
 // reads that pass the predicate, compacted on the device.
 // a * b as a 96-bit number (hi: bits 64.., lo: bits 0..63), exact
@@ -1001,19 +1008,12 @@ __host__ __device__ inline uint32_t dbf_window_keys(uint64_t cf, uint64_t cr, ui
     }
     return wt;
 }
-constexpr uint32_t DBF_NS = 16;                        // consecutive windows per lane (as SC_NS)
 constexpr uint64_t DBF_PIECE = 1ull << 26;             // windows per piece
 constexpr uint64_t DBF_PIECE_TEST = 4096;              // ... with KMER_DB_PIECE_TEST
-struct DbFasta {
-    const uint8_t *data;           // the rewritten FASTA: nothing outside [data, data + len) is loaded
-    uint64_t len;
-    const SeqLine *lines;          // by record (len 0: no windows)
-    const uint64_t *wbase2;        // by record: twice the index of its first window (scan of 2W)
-    uint64_t n_rec, total;         // records, windows of all records
-    uint64_t p0, m;                // the piece: windows [p0, p0 + m)
+struct DbFasta : WinWalk {                             // (the input is the rewritten FASTA, the lines its records)
     uint32_t k, plo, phi, pmask, canonical;
     uint32_t t0;                   // template index of record 0
-    uint32_t *cnt;                 // count pass: keys of each lane's windows (one per DBF_NS windows of the piece)
+    uint32_t *cnt;                 // count pass: keys of each lane's windows (one per WALK_NS windows of the piece)
     const uint64_t *off;           // write pass: their exclusive scan
     uint64_t *codes;               // write pass: the piece's pairs, in window order
     uint32_t *tmpl;

@@ -713,7 +713,7 @@ kmer_status match_build_table(kmer_match *m, kmerhip::TabProbe &a, const kmerhip
         return match_finish(m);
     }
     size_t bytes = 0;
-    MCHK(kmerhip::tab_probe_temp_bytes(n, &bytes));
+    MCHK(kmerhip::bucket_sort_bytes(n, &bytes));
     MCHK(db->tmp.ensure(bytes + 16));
     MCHK(db->pb_bkt.ensure(n));
     MCHK(db->pb_bkt2.ensure(n));

@@ -50,15 +50,9 @@ __device__ __forceinline__ void join_sync() {
 
 __device__ __forceinline__ uint32_t join_wave_sum(uint32_t x) { return readlane32(wave_incl_sum(x), 63); }
 
-// the Map value of entry e (class h) on one side; its big list is tiny: linear
-__device__ __forceinline__ uint64_t join_value(const TabBig *big, uint64_t n_big, uint64_t e, uint64_t h, bool dbl) {
-    uint64_t c = e & TAB_CMAX;
-    if (c == TAB_CMAX) {
-        c = 0;
-        for (uint64_t t = 0; t < n_big; ++t)
-            if (big[t].h == h) c = big[t].count;
-    }
-    return dbl ? 2 * c : c;
+// the Map value of entry e (class h) on one side
+__device__ __forceinline__ uint64_t join_value(const TabJoin &j, bool is_a, uint64_t e, uint64_t h, bool dbl) {
+    return tab_value(is_a ? j.a.big : j.b.big, is_a ? j.a.n_big : j.b.n_big, true, e, h, dbl);
 }
 
 // One class seen from the probing side: ep its entry there, es its entry on the
@@ -77,8 +71,8 @@ __device__ __forceinline__ uint32_t join_visit(const TabJoin &j, bool p_is_a, ui
     uint32_t n = j.a.canonical ? 1u : 2u;
     if (DECODE) n = tab_entry_keys(h, j.a.k, j.a.plo, j.a.phi, j.a.pmask, j.a.canonical != 0, keys, &dbl);
     if (!n) return 0;
-    const uint64_t vp = join_value(p_is_a ? j.a.big : j.b.big, p_is_a ? j.a.n_big : j.b.n_big, ep, h, dbl);
-    const uint64_t vs = es ? join_value(p_is_a ? j.b.big : j.a.big, p_is_a ? j.b.n_big : j.a.n_big, es, h, dbl) : 0;
+    const uint64_t vp = join_value(j, p_is_a, ep, h, dbl);
+    const uint64_t vs = es ? join_value(j, !p_is_a, es, h, dbl) : 0;
     const uint64_t va = p_is_a ? vp : vs, vb = p_is_a ? vs : vp;
     const bool in_a = va >= j.min_a, in_b = vb >= j.min_b;
     if (MODE == JM_COMPARE) {
@@ -111,7 +105,7 @@ __device__ __forceinline__ void join_own(const TabJoin &j, bool is_a, uint32_t q
     bool dbl = false;
     uint32_t n = j.a.canonical ? 1u : 2u;
     if (DECODE) n = tab_entry_keys(h, j.a.k, j.a.plo, j.a.phi, j.a.pmask, j.a.canonical != 0, keys, &dbl);
-    const uint64_t v = join_value(is_a ? j.a.big : j.b.big, is_a ? j.a.n_big : j.b.n_big, e, h, dbl);
+    const uint64_t v = join_value(j, is_a, e, h, dbl);
     const uint64_t na = is_a && v >= j.min_a ? n : 0u, nb = !is_a && v >= j.min_b ? n : 0u;
     acc[0] += na;
     acc[1] += nb;
@@ -127,15 +121,6 @@ __device__ __forceinline__ uint64_t join_find(const uint64_t *ent, uint64_t base
         if ((x >> 20) == rem && (x & TAB_CMAX)) es = x;
     }
     return es;
-}
-
-// write: t slots for this lane, one returning atomic for the wave (wave-uniform call)
-__device__ __forceinline__ uint64_t join_reserve(unsigned long long *cursor, uint32_t t, uint32_t lane) {
-    const uint32_t incl = wave_incl_sum(t);
-    const uint32_t total = readlane32(incl, 63);
-    uint64_t base = 0;
-    if (total && lane == 0) base = atomicAdd(cursor, (unsigned long long)total);
-    return readlane64(base, 0) + (incl - t);
 }
 
 __device__ __forceinline__ void join_put(const TabJoin &j, uint64_t slot, uint64_t key, uint64_t v) {
@@ -173,8 +158,8 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
     unsigned long long *tab = slices + (threadIdx.x >> 6) * JOIN_SLOTS;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t end_a = j.a.nd ? (j.a.start[TAB_NQ] < j.a.cap ? j.a.start[TAB_NQ] : j.a.cap) : 0;
-    const uint64_t end_b = j.b.nd ? (j.b.start[TAB_NQ] < j.b.cap ? j.b.start[TAB_NQ] : j.b.cap) : 0;
+    const uint64_t end_a = j.a.nd ? tab_end(j.a) : 0;
+    const uint64_t end_b = j.b.nd ? tab_end(j.b) : 0;
     const bool narrow = j.a.k <= TAB_NARROW_K;
     const uint32_t W = join_width(narrow);
     const bool swap = MODE != JM_COMPARE && j.op == JOIN_UNION && j.second;   // the lane path probes with B
@@ -212,7 +197,7 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                     const uint64_t ep = ent_p[bp + i];
                     t += join_visit<MODE, DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), acc, keys, &v);
                 }
-                uint64_t slot = join_reserve(j.n_out, t, lane);
+                uint64_t slot = wave_reserve(j.n_out, t, lane);
                 for (uint32_t i = 0; i < lp; ++i) {
                     const uint64_t ep = ent_p[bp + i];
                     const uint32_t n = join_visit<MODE, DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), acc, keys, &v);
@@ -336,7 +321,7 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                         }
                     }
                     if (MODE == JM_WRITE) {
-                        uint64_t slot = join_reserve(j.n_out, nt, lane);
+                        uint64_t slot = wave_reserve(j.n_out, nt, lane);
 #pragma unroll
                         for (uint32_t u = 0; u < JOIN_UNROLL; ++u) {
                             if (!ev[u]) continue;
@@ -360,12 +345,11 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
     if (MODE == JM_COMPARE) {
 #pragma unroll
         for (uint32_t i = 0; i < 8; ++i) {
-            uint64_t x = acc[i];
-            for (int d = 32; d >= 1; d >>= 1) x += (uint64_t)__shfl_xor((long long)x, d);
+            const uint64_t x = wave_sum(acc[i]);
             if (lane == 0 && x) atomicAdd(&j.sums[i], (unsigned long long)x);
         }
     } else if (MODE == JM_COUNT) {
-        for (int d = 32; d >= 1; d >>= 1) mine += (uint64_t)__shfl_xor((long long)mine, d);
+        mine = wave_sum(mine);
         if (lane == 0 && mine) atomicAdd(j.n_out, (unsigned long long)mine);
     }
 }

@@ -185,12 +185,8 @@ __device__ __forceinline__ uint32_t tab_round(const TabArgs &a, TabCur &c, bool 
                     if (q + j < end) x = (x & ~(0xFFu << (8 * j))) | ((uint32_t)q[j] << (8 * j));
             }
         }
-        const uint32_t lo4 = __builtin_amdgcn_udot4((x ^ (x >> 1)) & 0x02020202u, 0x08040201u, 0u, false) >> 1;
-        const uint32_t hi4 = __builtin_amdgcn_udot4(x & 0x04040404u, 0x08040201u, 0u, false) >> 2;
-        const uint32_t cc = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
-        const uint32_t ne = __builtin_amdgcn_perm(0u, 0x54474341u, cc) ^ x;      // 0 where the byte is A/C/G/T
-        const uint32_t nz = (((ne & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | ne) & 0x80808080u;
-        const uint32_t ex4 = __builtin_amdgcn_udot4(nz >> 7, 0x08040201u, 0u, false);
+        uint32_t lo4, hi4, ex4;
+        dword_planes(x, lo4, hi4, ex4);
         LO |= (uint64_t)lo4 << (4 * i);
         HI |= (uint64_t)hi4 << (4 * i);
         EX |= (uint64_t)ex4 << (4 * i);

@@ -124,10 +124,11 @@ def _fed(native, buf, nbytes, k, prefix, flags, cuts=None):
     return ctr
 
 
-def _check_all_ways(ctr, d, want):
-    """Host call, device call, host call again: all equal `want`; the table untouched."""
+def _check_all_ways(ctr, d, want, kb=None):
+    """Host call, device call, host call again: all equal `want`; the table untouched.
+    kb: the keys' bytes where they are not those of the digit rows d."""
     before = (ctr.table_digest(), ctr.table_stats())
-    kb = _key_bytes(d)
+    kb = _key_bytes(d) if kb is None else kb
     got = ctr.table_lookup(kb)
     assert got.dtype == np.uint64 and np.array_equal(got, want), int((got != want).sum())
     got = _ask_device(ctr, kb, len(d))
@@ -265,6 +266,23 @@ def test_lookup_scans_a_long_bucket(native, split):
     want = np.array([m.get(_key_bytes(row[None, :]), 0) for row in qs], dtype=np.uint64)
     assert (want == 3).sum() == 2 * len(range(0, 5000, 97)) and (want == 0).sum() == 10_000
     _check_all_ways(ctr, qs, want)
+    # A second order, for a scan that works on runs of neighbouring queries of
+    # one bucket: keys of the long bucket alternate, lane by lane, with random
+    # k-mers (empty buckets) and keys holding a non-A/C/G/T byte, so that runs
+    # of length 1 of the same bucket recur inside a wave; one present key is
+    # asked 130 times in a row (a whole wave of one remainder, across a wave
+    # edge); and the batch starts after 1 and after 63 other queries.
+    n = 2000
+    rows = _ACGT[np.stack([qs[:n], rng.integers(0, 4, (n, k), dtype=np.uint8), qs[n:2 * n]], axis=1)]
+    rows[np.arange(n), 2, rng.integers(0, k, n)] = ord("N")
+    rows = np.concatenate([rows[:n // 2].reshape(-1, k), np.repeat(_ACGT[written[97:98]], 130, axis=0),
+                           rows[n // 2:].reshape(-1, k)])
+    for shift in (1, 63):
+        kb = np.concatenate([_ACGT[rng.integers(0, 4, (shift, k), dtype=np.uint8)], rows])
+        want = np.array([m.get(row.tobytes(), 0) for row in kb], dtype=np.uint64)
+        assert (want[shift + 3 * (n // 2):][:130] == 3).all() and (want[shift:][0::3][:n // 2] > 0).sum() > n // 8
+        assert (want[shift:][2::3][:n // 2] == 0).all()
+        _check_all_ways(ctr, kb, want, kb.tobytes())
     ctr.close()
 
 
