@@ -251,6 +251,7 @@ kmer_status kmer_close(kmer_ctx *c) {
     c->bscan.release();
     c->hrec.release();
     c->hcnt.release();
+    c->hmark.release();
     c->tsum.release();
     c->tscan.release();
     c->hits.release();

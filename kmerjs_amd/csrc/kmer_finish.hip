@@ -116,9 +116,9 @@ kmer_status bucket_heads(kmer_ctx *c, uint64_t n, bool partial) {
             HIPCHK(c, hipMemsetAsync(c->bcur.p, 0, (uint64_t)BKT_MAX * BKT_CUR_STRIDE * sizeof(uint32_t), s));
         }
         HIPCHK(c, launch_bucket_onepass(c->rkey32.p, n, invalid, shift, nb, nblk, (uint32_t)cap, c->bcur.p, c->pkey16.p,
-                                        c->ridx2.p, c->hcnt.p, c->d_err, stamp, s));
-        HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, nullptr, nb, shift, c->hcnt.p, c->bcur.p, (uint32_t)cap, n,
-                                      c->d_err, s));
+                                        c->ridx2.p, c->hmark.p, c->d_err, stamp, s));
+        HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, nullptr, nb, shift, c->hmark.p, c->hcnt.p, c->bcur.p,
+                                      (uint32_t)cap, n, c->d_err, s));
         c->bkt_check = true;
         c->bkt_n = n;
         c->bkt_partial = partial;
@@ -130,10 +130,11 @@ kmer_status bucket_heads(kmer_ctx *c, uint64_t n, bool partial) {
     HIPCHK(c, c->ridx2.ensure(n, s));
     HIPCHK(c, c->bbase.ensure(2 * BKT_MAX + 2, s));   // bucket totals [0, nb), starts [BKT_MAX, BKT_MAX + nb]
     uint32_t *btot = c->bbase.p, *bstart = c->bbase.p + BKT_MAX;
-    HIPCHK(c, launch_bucket_hist(c->rkey32.p, n, invalid, shift, nb, nblk, c->bH.p, c->hcnt.p, stamp, s));
+    HIPCHK(c, launch_bucket_hist(c->rkey32.p, n, invalid, shift, nb, nblk, c->bH.p, c->hmark.p, stamp, s));
     HIPCHK(c, launch_bucket_offsets(c->bH.p, nb, nblk, c->bHs.p, btot, bstart, c->d_bticket, s));
     HIPCHK(c, launch_bucket_scatter(c->rkey32.p, n, invalid, shift, nb, nblk, c->bHs.p, bstart, c->pkey16.p, c->ridx2.p, s));
-    HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, bstart, nb, shift, c->hcnt.p, nullptr, 0, n, c->d_err, s));
+    HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, bstart, nb, shift, c->hmark.p, c->hcnt.p, nullptr, 0, n, c->d_err,
+                                  s));
     return KMER_OK;
 }
 
@@ -250,7 +251,8 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
     }
     const uint64_t invalid = c->kbits >= 63 ? ~0ull : (1ull << c->kbits);
     kmer_status st;
-    const bool bucket = bucket_route(c, with_counts);
+    const bool bucket = !c->wide && bucket_route(c, with_counts);
+    if (bucket) HIPCHK(c, c->hmark.ensure(n + 16, s));   // (head marks: a byte per rank, hcnt only for counts >= 255)
     if (c->wide)
         st = sort_and_heads_wide(c, n);          // (no partials / merged counts: refused for wide keys)
     else if (bucket)
@@ -264,7 +266,7 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
     // scanned here when there are many workgroups)
     const uint64_t nbe = emit_blocks(n);
     HIPCHK(c, c->ecnt.ensure(nbe, s));
-    HIPCHK(c, launch_head_count(c->hcnt.p, n, c->ecnt.p, s));
+    HIPCHK(c, launch_head_count(c->hcnt.p, bucket ? c->hmark.p : nullptr, n, c->ecnt.p, s));
     EmitArgs e;
     memset(&e, 0, sizeof(e));
     e.ecnt = c->ecnt.p;
@@ -275,6 +277,7 @@ kmer_status rank_finish(kmer_ctx *c, uint64_t n, bool partial, bool with_counts,
         e.epre = c->epre.p;
     }
     e.hcnt = c->hcnt.p;
+    e.hmark = bucket ? c->hmark.p : nullptr;
     e.hrec = with_counts ? c->hrec.p : nullptr;
     e.rkey32 = c->narrow ? c->rkey32.p : nullptr;
     e.rkey64 = c->narrow ? nullptr : c->rkey.p;

@@ -172,6 +172,7 @@ struct kmer_ctx {
     DBuf<uint64_t> epre;
     DBuf<HeadRec> hrec;
     DBuf<uint32_t> hcnt;           // by rank: != 0 iff first occurrence of its key (bucket finish: count)
+    DBuf<uint8_t> hmark;           // bucket finish: min(count, 255) by rank; hcnt holds a rank's count only where this is 255
     DBuf<uint32_t> bH, bHs;        // bucket finish: per (bucket, block) counts, their scan
     DBuf<uint16_t> pkey16;         // bucket finish: low key bits, partitioned
     DBuf<uint32_t> bcur;           // one-pass partition: bucket cursors (BKT_CUR_STRIDE apart; 0 between finishes)

@@ -247,6 +247,7 @@ struct HeadRec {
 // Ordered output from the rank arrays after the key sort.
 struct EmitArgs {
     const uint32_t *hcnt;          // by rank: the key's count at its first occurrence, else 0
+    const uint8_t *hmark;          // bucket routes: min(that count, 255) by rank, hcnt valid only where it is 255; or null
     const HeadRec *hrec;           // merged finish (summed counts): by rank, key and u64 count of heads; else null
     const uint32_t *rkey32;        // hrec == null: key by rank (narrow keys) ...
     const uint64_t *rkey64;        // ... or (wider keys)
@@ -432,7 +433,7 @@ hipError_t launch_heads_sparse(const uint64_t *skey64, const uint32_t *skey32, c
 hipError_t launch_heads32(const uint32_t *skey, const uint32_t *srank, uint64_t n, uint32_t invalid_key,
                           const uint64_t *rcnt, HeadRec *hrec, uint32_t *hcnt, hipStream_t s);
 hipError_t launch_emit(const EmitArgs &a, hipStream_t s);
-hipError_t launch_head_count(const uint32_t *hcnt, uint64_t n, uint32_t *ecnt, hipStream_t s);
+hipError_t launch_head_count(const uint32_t *hcnt, const uint8_t *hmark, uint64_t n, uint32_t *ecnt, hipStream_t s);
 uint64_t emit_blocks(uint64_t n);
 constexpr uint64_t EMIT_DIRECT_MAX = 4096;   // emit workgroups that sum the earlier counts themselves (O(n^2) reads)
 // wide keys (2(k - |P|) >= 64 bits, k <= 64): dst[i] = src[idx[i]]; the cross
@@ -459,9 +460,9 @@ constexpr uint32_t BKT_CUR_STRIDE = 32;      // one-pass partition: one bucket c
 inline uint64_t bucket_cap(uint64_t n, uint32_t nb) { return (n + nb - 1) / nb * 3 / 2 + BKT_EPB_HOST; }
 hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
                                  uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
-                                 uint32_t *hcnt, unsigned int *err, uint64_t *stamp, hipStream_t s);
+                                 uint8_t *hmark, unsigned int *err, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_hist(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, uint64_t *stamp, hipStream_t s);
+                              uint32_t nblk, uint32_t *H, uint8_t *hmark, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_offsets(const uint32_t *H, uint32_t nb, uint32_t nblk, uint32_t *Hs, uint32_t *btot,
                                  uint32_t *bbase, unsigned int *ticket, hipStream_t s);
 hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
@@ -469,7 +470,7 @@ hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t inval
                                  uint32_t *prank, hipStream_t s);
 // (cur != null: the one-pass route's regions of `cap` entries, totals in the cursors, which it returns to 0)
 hipError_t launch_bucket_heads(const uint16_t *pkey, const uint32_t *prank, const uint32_t *bbase, uint32_t nb,
-                               uint32_t shift, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
+                               uint32_t shift, uint8_t *hmark, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
                                unsigned int *err, hipStream_t s);
 // multi-GPU hit exchange (kmer_exchange_prepare / kmer_finish_exchanged)
 struct XHit {

@@ -2605,20 +2605,34 @@ __global__ __launch_bounds__(256) void heads_wide_kernel(const uint64_t *shi, co
 // ---------------------------------------------------------------------------
 constexpr uint32_t BKT_EPB = 4096;           // elements per partition block
 
+// Head marks: on the bucket routes a rank's head count is kept as one byte,
+// hmark[r] = min(count, HMARK_FULL) (0: not a first occurrence), and a count
+// of HMARK_FULL or more also in full in hcnt[r], which is read only there and
+// never cleared.  The marks of all ranks are a quarter of hcnt's bytes to
+// clear, to scatter into from every XCD and to read twice.
+constexpr uint32_t HMARK_FULL = 255;
+// clear the marks of a partition block's ranks (bucket_heads sets the heads')
+__device__ __forceinline__ void clear_head_marks(uint8_t *hmark, uint64_t base, uint64_t n) {
+    static_assert(BKT_EPB == 16 * 256, "16 marks per thread");
+    const uint64_t i = base + 16 * threadIdx.x;
+    if (i + 16 <= n) *(uint4 *)(hmark + i) = make_uint4(0, 0, 0, 0);
+    else for (uint64_t t = i; t < n; ++t) hmark[t] = 0;
+}
+__device__ __forceinline__ uint32_t head_count_at(const uint8_t *hmark, const uint32_t *hcnt, uint64_t r) {
+    if (!hmark) return hcnt[r];
+    const uint32_t m = hmark[r];
+    return m == HMARK_FULL ? hcnt[r] : m;
+}
+
 __global__ __launch_bounds__(256) void bucket_hist_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
                                                           uint32_t shift, uint32_t nb, uint32_t nblk,
-                                                          uint32_t *H, uint32_t *hcnt, uint64_t *stamp) {
+                                                          uint32_t *H, uint8_t *hmark, uint64_t *stamp) {
     stamp_now(stamp, STAMP_FINISH_START);
     __shared__ uint32_t hist[BKT_MAX];
     for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[b] = 0;
     __syncthreads();
     const uint64_t base = (uint64_t)blockIdx.x * BKT_EPB;
-    // clear the head counts of this block's ranks (bucket_heads sets the heads')
-    for (uint32_t j = 4 * threadIdx.x; j < BKT_EPB; j += 4 * 256) {
-        const uint64_t i = base + j;
-        if (i + 4 <= n) *(uint4 *)(hcnt + i) = make_uint4(0, 0, 0, 0);
-        else for (uint64_t t = i; t < n; ++t) hcnt[t] = 0;
-    }
+    clear_head_marks(hmark, base, n);
 #pragma unroll 4
     for (uint32_t j = threadIdx.x; j < BKT_EPB; j += 256) {
         const uint64_t i = base + j;
@@ -2791,7 +2805,7 @@ constexpr uint32_t BKT_SKIP = 0x80000000u;   // one-pass partition: a run that d
 // the finish with the counted kernels.  nb * cap < 2^31 (launcher).
 __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
                                                              uint32_t shift, uint32_t nb, uint32_t cap, uint32_t *cur,
-                                                             uint16_t *pkey, uint32_t *prank, uint32_t *hcnt,
+                                                             uint16_t *pkey, uint32_t *prank, uint8_t *hmark,
                                                              unsigned int *err, uint64_t *stamp) {
     stamp_now(stamp, STAMP_FINISH_START);
     __shared__ uint32_t cnt[BKT_MAX];          // per bucket: count, then local start, then global position
@@ -2801,12 +2815,7 @@ __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key
     for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
     __syncthreads();
     const uint64_t base = (uint64_t)blockIdx.x * BKT_EPB;
-    // clear the head counts of this block's ranks (bucket_heads sets the heads')
-    for (uint32_t j = 4 * threadIdx.x; j < BKT_EPB; j += 4 * 256) {
-        const uint64_t i = base + j;
-        if (i + 4 <= n) *(uint4 *)(hcnt + i) = make_uint4(0, 0, 0, 0);
-        else for (uint64_t t = i; t < n; ++t) hcnt[t] = 0;
-    }
+    clear_head_marks(hmark, base, n);
     uint32_t kk[BKT_EPB / 256], li[BKT_EPB / 256];
 #pragma unroll
     for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
@@ -2886,8 +2895,8 @@ __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key
 // total), the total read from the bucket's cursor, which goes back to 0 for
 // the next finish; a bucket past its region is skipped: its finish is redone)
 __global__ __launch_bounds__(1024) void bucket_heads_kernel(const uint16_t *pkey, const uint32_t *prank,
-                                                            const uint32_t *bbase, uint32_t shift, uint32_t *hcnt,
-                                                            uint32_t *cur, uint32_t cap, uint64_t n,
+                                                            const uint32_t *bbase, uint32_t shift, uint8_t *hmark,
+                                                            uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
                                                             unsigned int *err) {
     __shared__ uint32_t minr[1u << BKT_LOW];
     __shared__ uint32_t cnt[1u << BKT_LOW];
@@ -2931,19 +2940,31 @@ __global__ __launch_bounds__(1024) void bucket_heads_kernel(const uint16_t *pkey
         const uint32_t c = cnt[j];
         if (c) {
             const uint32_t r = minr[j];
-            if (r < n) hcnt[r] = c;     // (the key is rkey32 at that rank)
-            else atomicOr(err, ERR_BKT_RANK);
+            if (r < n) {                // (the key is rkey32 at that rank)
+                hmark[r] = (uint8_t)min(c, HMARK_FULL);
+                if (c >= HMARK_FULL) hcnt[r] = c;
+            } else {
+                atomicOr(err, ERR_BKT_RANK);
+            }
         }
     }
 }
 
 // Heads (hcnt != 0) per EMIT_RPB ranks: the emit workgroups' prefixes.
 constexpr uint32_t EMIT_RPB = 1024;
-__global__ __launch_bounds__(256) void head_count_kernel(const uint32_t *hcnt, uint64_t n, uint32_t *ecnt) {
+__global__ __launch_bounds__(256) void head_count_kernel(const uint32_t *hcnt, const uint8_t *hmark, uint64_t n,
+                                                         uint32_t *ecnt) {
     __shared__ uint32_t ws[4];
     const uint64_t r0 = (uint64_t)blockIdx.x * EMIT_RPB + 4 * threadIdx.x;
     uint32_t c = 0;
-    if (r0 + 4 <= n) {
+    if (hmark) {                                 // (the bucket routes: a byte per rank)
+        if (r0 + 4 <= n) {
+            const uint32_t v = *(const uint32_t *)(hmark + r0);
+            c = ((v & 0xFFu) != 0) + ((v & 0xFF00u) != 0) + ((v & 0xFF0000u) != 0) + ((v & 0xFF000000u) != 0);
+        } else {
+            for (uint64_t r = r0; r < n; ++r) c += hmark[r] != 0;
+        }
+    } else if (r0 + 4 <= n) {
         const uint4 v = *(const uint4 *)(hcnt + r0);
         c = (v.x != 0) + (v.y != 0) + (v.z != 0) + (v.w != 0);
     } else {
@@ -2981,7 +3002,7 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
         const uint64_t r = rb + 256 * i + tid;
-        hcr[i] = r < n ? a.hcnt[r] : 0u;
+        hcr[i] = r < n ? head_count_at(a.hmark, a.hcnt, r) : 0u;
         hm[i] = __ballot(hcr[i] != 0);
         if (lane == 0) s_w[i][wid] = (uint32_t)__popcll(hm[i]);
     }
@@ -3647,8 +3668,8 @@ hipError_t launch_heads32(const uint32_t *skey, const uint32_t *srank, uint64_t 
     return hipGetLastError();
 }
 hipError_t launch_bucket_hist(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                              uint32_t nblk, uint32_t *H, uint32_t *hcnt, uint64_t *stamp, hipStream_t s) {
-    hipLaunchKernelGGL(bucket_hist_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, nblk, H, hcnt,
+                              uint32_t nblk, uint32_t *H, uint8_t *hmark, uint64_t *stamp, hipStream_t s) {
+    hipLaunchKernelGGL(bucket_hist_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, nblk, H, hmark,
                        stamp);
     return hipGetLastError();
 }
@@ -3666,23 +3687,23 @@ hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t inval
 }
 hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
                                  uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
-                                 uint32_t *hcnt, unsigned int *err, uint64_t *stamp, hipStream_t s) {
+                                 uint8_t *hmark, unsigned int *err, uint64_t *stamp, hipStream_t s) {
     // (region addresses are 32-bit, and BKT_SKIP must not be one of them)
     if (nb == 0 || nb > BKT_MAX || (uint64_t)nb * cap > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bucket_onepass_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, cap, cur, pkey,
-                       prank, hcnt, err, stamp);
+                       prank, hmark, err, stamp);
     return hipGetLastError();
 }
 hipError_t launch_bucket_heads(const uint16_t *pkey, const uint32_t *prank, const uint32_t *bbase, uint32_t nb,
-                               uint32_t shift, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
+                               uint32_t shift, uint8_t *hmark, uint32_t *hcnt, uint32_t *cur, uint32_t cap, uint64_t n,
                                unsigned int *err, hipStream_t s) {
-    hipLaunchKernelGGL(bucket_heads_kernel, dim3(nb), dim3(1024), 0, s, pkey, prank, bbase, shift, hcnt, cur, cap, n,
-                       err);
+    hipLaunchKernelGGL(bucket_heads_kernel, dim3(nb), dim3(1024), 0, s, pkey, prank, bbase, shift, hmark, hcnt, cur, cap,
+                       n, err);
     return hipGetLastError();
 }
 uint64_t emit_blocks(uint64_t n) { return (n + EMIT_RPB - 1) / EMIT_RPB; }
-hipError_t launch_head_count(const uint32_t *hcnt, uint64_t n, uint32_t *ecnt, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(head_count_kernel, dim3((uint32_t)emit_blocks(n)), dim3(256), 0, s, hcnt, n, ecnt);
+hipError_t launch_head_count(const uint32_t *hcnt, const uint8_t *hmark, uint64_t n, uint32_t *ecnt, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(head_count_kernel, dim3((uint32_t)emit_blocks(n)), dim3(256), 0, s, hcnt, hmark, n, ecnt);
     return hipGetLastError();
 }
 hipError_t launch_emit(const EmitArgs &a, hipStream_t s) {
