@@ -168,6 +168,14 @@ __device__ __forceinline__ uint64_t revcomp_code(uint64_t x, uint32_t k) {
     return k >= 32 ? x : (x >> (64 - 2 * k));
 }
 
+// ... of 16 bases: 32 bits, the byte swap one v_perm
+__device__ __forceinline__ uint32_t revcomp_code16(uint32_t x) {
+    x = ~x;
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    return __builtin_bswap32(x);
+}
+
 // the same for a 128-bit code of 32 < k <= 64 bases (hi: the first k - 32)
 __device__ __forceinline__ void revcomp_code128(uint64_t hi, uint64_t lo, uint32_t k, uint64_t *rhi, uint64_t *rlo) {
     const uint64_t h = revcomp_code(lo, 32), l = revcomp_code(hi, 32);   // the 128 bits reversed
@@ -1048,48 +1056,58 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(8))) void s
 // order key (line << (pbits + 1) | strand << pbits | strand ? maxrel - rel : rel).
 // Returns the packed key (invalid_key when the hit does not count as a packed
 // key: non-sequence line, or a record) and writes records for exotic windows
-// / record mode.  *lk = order of the hit among its tile's hits (local).
+// / record mode.  *lk = order of the hit among its tile's hits (local), 31
+// bits.  DEF: the default shape compiled in -- k = 16, |P| = 5, packed narrow
+// keys (rkey32), pbits = PBITS_DEFAULT -- so the shifts, the suffix mask and
+// the reverse complement are constants and the k > 32 / wide / record-mode
+// tests are gone.
+template <bool DEF>
 __device__ __forceinline__ uint64_t resolve_hit(const HitArgs &a, uint64_t pos_lines, const HitRec &r,
                                                 uint64_t code_hi, const TileSum &tb, uint64_t *order_out,
                                                 uint32_t *lk, bool *lvalid_out, uint64_t *key_hi) {
+    const uint32_t k = DEF ? 16u : a.k, plen = DEF ? 5u : a.plen, pbits = DEF ? PBITS_DEFAULT : a.pbits;
+    const bool wide = DEF ? false : a.wide != 0, packed = DEF ? true : a.packed != 0;
+    const uint64_t smask = DEF ? (1ull << 22) - 1ull : a.smask, invalid_key = DEF ? 1ull << 22 : a.invalid_key;
     const uint32_t t = r.tile;
     const uint32_t strand = (r.qm >> 14) & 1u;
     const bool exotic = (r.qm >> 15) & 1u;
     const bool lvalid = (r.qm >> 16) & 1u;
     const int q = (int)(r.qm & 0x3FFFu);
-    const int s0 = strand ? q + (int)a.plen - (int)a.k : q;     // >= -63
-    const uint64_t tile_abs = a.abs_offset + (uint64_t)t * TILE;
+    const int s0 = strand ? q + (int)plen - (int)k : q;         // >= -63
     const uint64_t li = pos_lines + tb.cnt + r.c_local;
-    const uint64_t lstart = lvalid ? tile_abs + r.lstart : tb.lnl;
-    const uint64_t sabs = tile_abs + (uint64_t)(int64_t)s0;
-    uint64_t rel = sabs - lstart;
+    // the line starts inside the tile: tile-relative, 32 bits; else from the
+    // last '\n' of the tiles before (absolute)
+    uint64_t rel = (uint64_t)(int64_t)(s0 - (int)r.lstart);
+    if (!lvalid) rel = a.abs_offset + (uint64_t)t * TILE + (uint64_t)(int64_t)s0 - tb.lnl;
     const bool seq = (li & 3) == 1;
-    const uint64_t maxrel = (1ull << a.pbits) - 1ull;
+    const uint64_t maxrel = (1ull << pbits) - 1ull;
     if (rel > maxrel) {
         if (seq) atomicOr(a.err, ERR_LINE_TOO_LONG);
         rel = maxrel;                            // (non-sequence lines only need a consistent order)
     }
-    if (li >> (63 - a.pbits)) atomicOr(a.err, ERR_LINE_TOO_LONG);   // (line field full: long-line mode)
-    const uint64_t order = (li << (a.pbits + 1)) | ((uint64_t)strand << a.pbits) | (strand ? maxrel - rel : rel);
+    if (li >> (63 - pbits)) atomicOr(a.err, ERR_LINE_TOO_LONG);   // (line field full: long-line mode)
+    const uint64_t order = (li << (pbits + 1)) | ((uint64_t)strand << pbits) | (strand ? maxrel - rel : rel);
     *order_out = order;
     const uint32_t sp = (uint32_t)(s0 + 64);     // < 2^15
-    *lk = (r.c_local << 17) | (strand << 16) | (strand ? 0xFFFFu - sp : sp);
+    *lk = (r.c_local << 16) | (strand << 15) | (strand ? 0x7FFFu - sp : sp);   // (c_local <= 2^14)
     *lvalid_out = lvalid;
-    uint64_t key = a.invalid_key;
-    *key_hi = a.wide ? a.invalid_key : 0;        // (wide: the invalid marker is in the high word)
-    if (a.wide) key = 0;
+    uint64_t key = invalid_key;
+    *key_hi = wide ? invalid_key : 0;            // (wide: the invalid marker is in the high word)
+    if (wide) key = 0;
     if (seq) {
-        if (a.packed && !exotic) {
-            if (a.k > 32) {
+        if (packed && !exotic) {
+            if (DEF) {
+                key = (strand ? revcomp_code16((uint32_t)r.code) : (uint32_t)r.code) & (uint32_t)smask;
+            } else if (k > 32) {
                 uint64_t h = code_hi, l = r.code;
-                if (strand) revcomp_code128(code_hi, r.code, a.k, &h, &l);
-                key = l & a.smask;
+                if (strand) revcomp_code128(code_hi, r.code, k, &h, &l);
+                key = l & smask;
                 *key_hi = h & a.smask_hi;
             } else {
-                key = (strand ? revcomp_code(r.code, a.k) : r.code) & a.smask;
+                key = (strand ? revcomp_code(r.code, k) : r.code) & smask;
             }
         } else {
-            append_record(a.recs, a.rec_count, a.rec_cap, a.err, order, (uint64_t)t * TILE + (uint64_t)(int64_t)s0, a.k,
+            append_record(a.recs, a.rec_count, a.rec_cap, a.err, order, (uint64_t)t * TILE + (uint64_t)(int64_t)s0, k,
                           strand);
         }
     }
@@ -1097,22 +1115,24 @@ __device__ __forceinline__ uint64_t resolve_hit(const HitArgs &a, uint64_t pos_l
 }
 
 // Write one resolved packed hit at its rank slot, or to the cross list.
+template <bool DEF>
 __device__ __forceinline__ void place_hit(const HitArgs &a, uint64_t slot, bool cross, uint64_t xi, uint64_t key,
                                           uint64_t key_hi, uint64_t order) {
+    const bool wide = DEF ? false : a.wide != 0;
     // (no rank payload: the finish sorts (key, iota))
     if (!cross) {
         if (slot >= a.rcap) {                    // only when hits overflowed the lists: redone
             atomicOr(a.err, ERR_OVF_OVERFLOW);
             return;
         }
-        if (a.rkey32) a.rkey32[slot] = (uint32_t)key;
+        if (DEF || a.rkey32) a.rkey32[slot] = (uint32_t)key;
         else a.rkey[slot] = key;
-        if (a.wide) a.rkeyh[slot] = key_hi;
+        if (wide) a.rkeyh[slot] = key_hi;
         a.rord[slot] = order;
     } else if (xi < a.xcap) {
         a.xord[xi] = order;
         a.xslot[xi] = (uint32_t)slot;
-        if (a.wide) {                            // (the cross kernels move the index; cross_wide_fix the key)
+        if (wide) {                              // (the cross kernels move the index; cross_wide_fix the key)
             a.xkey[xi] = xi;
             a.xkeyl[xi] = key;
             a.xkeyh[xi] = key_hi;
@@ -1126,104 +1146,113 @@ __device__ __forceinline__ void place_hit(const HitArgs &a, uint64_t slot, bool 
 
 // Hits of HTPW consecutive tiles per wave, flattened onto the lanes (a tile
 // has ~14 hits at 150 bp reads: one tile per wave would leave most lanes
-// idle).  Phase 1: lane = one hit: resolve it, stage (local order, cross
-// flag, key, order) in LDS.  Phase 2: rank each hit among its tile's hits by
-// (line, strand, +-offset) and place it at out_base + hits-before-tile +
-// rank, or on the cross list (line crosses a tile edge / tile overflowed).
+// idle).  Phase 1: lane = one hit: resolve it, stage (key, order) in LDS and
+// its local order with the cross flag in bit 0 as one word, in the tile's own
+// row of HMAX words (unused words: ~0, which ranks behind every hit).  Phase
+// 2: rank each hit among its tile's hits by (line, strand, +-offset) -- four
+// words per LDS read, as many reads as the wave's largest tile needs -- and
+// place it at out_base + hits-before-tile + rank, or on the cross list (line
+// crosses a tile edge / tile overflowed).
 constexpr uint32_t HTPW = 4;
 constexpr uint32_t HENT = HTPW * HMAX;       // staged hits per wave
-template <bool WIDE>
+static_assert(HENT * 4 == 64 * 16, "the wave clears its rows with one 16-byte store per lane");
+template <bool WIDE, bool DEF>
 __global__ __launch_bounds__(256) void hit_kernel(HitArgs a) {
-    __shared__ uint32_t s_lk[4][HENT];
-    __shared__ uint8_t s_x[4][HENT];
-    __shared__ uint64_t s_key[4][HENT];
+    static_assert(!(WIDE && DEF), "the default shape has narrow keys");
+    __shared__ __attribute__((aligned(16))) uint32_t s_lk[4][HENT];
+    __shared__ uint64_t s_key[DEF ? 1 : 4][DEF ? 1 : HENT];
+    __shared__ uint32_t s_key32[DEF ? 4 : 1][DEF ? HENT : 1];
     __shared__ uint64_t s_ord[4][HENT];
     __shared__ uint64_t s_keyh[WIDE ? 4 : 1][WIDE ? HENT : 1];
     const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t t0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + wid) * HTPW);
     if (t0 >= a.n_tiles) return;
     // (the overflow count, the stream position and the tiles' sums issued
-    // together: one memory round trip before the hits, not three)
+    // together: one memory round trip before the hits, not three).  Lane l
+    // holds the sums of tile t0 + (l & 3); a hit's lane pulls its tile's
+    // fields from lane u (ds_bpermute: one op per field, every lane active)
     const unsigned long long ovf = *a.ovf_count;
     const uint64_t pos_lines = a.pos->lines;
-    TileSum ts[HTPW], tb[HTPW];
-#pragma unroll
-    for (uint32_t u = 0; u < HTPW; ++u) {
-        const uint32_t t = min(t0 + u, a.n_tiles - 1);
-        ts[u] = a.tsum[t];
-        tb[u] = a.tscan[t];
-    }
+    const uint32_t tl = min(t0 + (lane & 3u), a.n_tiles - 1);
+    const TileSum tsl = a.tsum[tl], tbl = a.tscan[tl];
+    ((uint4 *)s_lk[wid])[lane] = make_uint4(~0u, ~0u, ~0u, ~0u);
     if (ovf > a.ovf_cap) return;                 // overflowed scan: the host redoes the chunk
-    uint32_t off[HTPW + 1];
+    const uint32_t nl = t0 + (lane & 3u) < a.n_tiles ? min(tsl.nh, (uint32_t)HMAX) : 0u;
+    uint32_t off[HTPW + 1], nmax = 0;
     off[0] = 0;
 #pragma unroll
-    for (uint32_t u = 0; u < HTPW; ++u) off[u + 1] = off[u] + (t0 + u < a.n_tiles ? min(ts[u].nh, (uint32_t)HMAX) : 0u);
+    for (uint32_t u = 0; u < HTPW; ++u) {
+        const uint32_t nu = readlane32(nl, u);
+        off[u + 1] = off[u] + nu;
+        nmax = max(nmax, nu);
+    }
     const uint32_t total = off[HTPW];
+    auto pull = [](uint32_t u, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(u << 2), (int)v); };
+    auto pull64 = [&](uint32_t u, uint64_t v) {
+        return ((uint64_t)pull(u, (uint32_t)(v >> 32)) << 32) | pull(u, (uint32_t)v);
+    };
     // phase 1
     for (uint32_t e0 = 0; e0 < total; e0 += 64) {
         const uint32_t e = e0 + lane;
+        uint32_t u = 0;
+#pragma unroll
+        for (uint32_t v = 1; v < HTPW; ++v) u += e >= off[v] ? 1u : 0u;
+        // (only the fields this phase uses)
+        const uint32_t lo = u == 0 ? off[0] : u == 1 ? off[1] : u == 2 ? off[2] : off[3];
+        const uint32_t nh = pull(u, tsl.nh), cnt = pull(u, (uint32_t)tsl.cnt);
+        TileSum tbu;
+        tbu.cnt = pull64(u, tbl.cnt);
+        tbu.lnl = pull64(u, tbl.lnl);
+        tbu.nh = tbu.nx = 0;
         if (e < total) {
-            uint32_t u = 0;
-#pragma unroll
-            for (uint32_t v = 1; v < HTPW; ++v) u += e >= off[v] ? 1u : 0u;
-            const uint32_t i = e - off[u];
-            TileSum tsu = ts[0], tbu = tb[0];
-#pragma unroll
-            for (uint32_t v = 1; v < HTPW; ++v)
-                if (u == v) {
-                    tsu = ts[v];
-                    tbu = tb[v];
-                }
+            const uint32_t i = e - lo;
             const uint64_t hslot = (uint64_t)(t0 + u) * HMAX + i;
             const HitRec r = a.hits[hslot];
             uint64_t order, kh;
             uint32_t lk;
             bool lvalid;
-            const uint64_t key = resolve_hit(a, pos_lines, r, a.k > 32 ? a.hits_hi[hslot] : 0, tbu, &order, &lk, &lvalid,
-                                             &kh);
-            s_lk[wid][e] = lk;
-            s_x[wid][e] = (tsu.nh > (uint32_t)HMAX || !lvalid || r.c_local == (uint32_t)tsu.cnt) ? 1 : 0;
-            s_key[wid][e] = key;
+            const uint64_t key = resolve_hit<DEF>(a, pos_lines, r, !DEF && a.k > 32 ? a.hits_hi[hslot] : 0, tbu, &order,
+                                                  &lk, &lvalid, &kh);
+            const uint32_t x = (nh > (uint32_t)HMAX || !lvalid || r.c_local == cnt) ? 1u : 0u;
+            s_lk[wid][u * HMAX + i] = (lk << 1) | x;
+            if (DEF) s_key32[DEF ? wid : 0][DEF ? e : 0] = (uint32_t)key;
+            else s_key[DEF ? 0 : wid][DEF ? 0 : e] = key;
             if (WIDE) s_keyh[WIDE ? wid : 0][WIDE ? e : 0] = kh;
             s_ord[wid][e] = order;
         }
     }
-    if (!a.packed) return;
+    if (!DEF && !a.packed) return;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     // phase 2
     for (uint32_t e0 = 0; e0 < total; e0 += 64) {
         const uint32_t e = e0 + lane;
-        if (e >= total) continue;
         uint32_t u = 0;
 #pragma unroll
         for (uint32_t v = 1; v < HTPW; ++v) u += e >= off[v] ? 1u : 0u;
-        uint32_t lo = off[0], hi = off[1], nh = ts[0].nh;
-        uint64_t hb = tb[0].nh, xb = tb[0].nx;
-#pragma unroll
-        for (uint32_t v = 1; v < HTPW; ++v)
-            if (u == v) {
-                lo = off[v];
-                hi = off[v + 1];
-                nh = ts[v].nh;
-                hb = tb[v].nh;
-                xb = tb[v].nx;
-            }
+        const uint32_t lo = u == 0 ? off[0] : u == 1 ? off[1] : u == 2 ? off[2] : off[3];
+        const uint32_t nh = pull(u, tsl.nh), hb = pull(u, tbl.nh), xb = pull(u, tbl.nx);
+        if (e >= total) continue;
         const uint32_t i = e - lo;
-        const bool cross = s_x[wid][e] != 0;
-        uint32_t rank = i, xr = i;            // overflowed tile: the in-tile ordinal
-        if (nh <= (uint32_t)HMAX) {
-            const uint32_t lk = s_lk[wid][e];
-            rank = 0;
-            xr = 0;
-            for (uint32_t j = lo; j < hi; ++j) {
-                const uint32_t less = s_lk[wid][j] < lk ? 1u : 0u;
-                rank += less;
-                xr += less & (uint32_t)s_x[wid][j];
-            }
+        const uint32_t *row = &s_lk[wid][u * HMAX];
+        const uint32_t lkx = row[i], mine = lkx & ~1u;
+        const bool cross = lkx & 1u;
+        // entries that rank before this one: 256 each, + 1 for a cross one
+        // (an entry's word < mine <=> its local order is smaller; <= 64 of each)
+        uint32_t acc = 0;
+#pragma clang loop vectorize(disable) unroll(disable)   // (a plain loop: the set-up of a wider one costs more than it saves)
+        for (uint32_t j = 0; j < nmax; j += 4) {  // (uniform: the wave's largest tile)
+            const uint4 w = *(const uint4 *)(row + j);
+            acc += w.x < mine ? (w.x & 1u) | 256u : 0u;
+            acc += w.y < mine ? (w.y & 1u) | 256u : 0u;
+            acc += w.z < mine ? (w.z & 1u) | 256u : 0u;
+            acc += w.w < mine ? (w.w & 1u) | 256u : 0u;
         }
-        place_hit(a, a.out_base + hb + rank, cross, a.xbase + xb + xr, s_key[wid][e],
-                  WIDE ? s_keyh[WIDE ? wid : 0][WIDE ? e : 0] : 0, s_ord[wid][e]);
+        uint32_t rank = acc >> 8, xr = acc & 0xFFu;
+        if (nh > (uint32_t)HMAX) rank = xr = i;  // overflowed tile: the in-tile ordinal
+        place_hit<DEF>(a, a.out_base + hb + rank, cross, a.xbase + xb + xr,
+                       DEF ? (uint64_t)s_key32[DEF ? wid : 0][DEF ? e : 0] : s_key[DEF ? 0 : wid][DEF ? 0 : e],
+                       WIDE ? s_keyh[WIDE ? wid : 0][WIDE ? e : 0] : 0, s_ord[wid][e]);
     }
 }
 
@@ -1236,10 +1265,10 @@ __global__ __launch_bounds__(256) void hit_overflow_kernel(HitArgs a) {
         uint64_t order, kh;
         uint32_t lk;
         bool lvalid;
-        const uint64_t key = resolve_hit(a, a.pos->lines, r, a.k > 32 ? a.ovf_hi[i] : 0, tb, &order, &lk, &lvalid, &kh);
+        const uint64_t key = resolve_hit<false>(a, a.pos->lines, r, a.k > 32 ? a.ovf_hi[i] : 0, tb, &order, &lk, &lvalid, &kh);
         if (!a.packed) continue;
         const uint32_t ord = r.qm >> 17;
-        place_hit(a, a.out_base + tb.nh + ord, true, a.xbase + tb.nx + ord, key, kh, order);
+        place_hit<false>(a, a.out_base + tb.nh + ord, true, a.xbase + tb.nx + ord, key, kh, order);
     }
     // chunk tail, by the last block to finish (every hit of the chunk has read
     // pos by then): advance the stream position past the chunk, publish the
@@ -2955,20 +2984,25 @@ constexpr uint32_t EMIT_RPB = 1024;
 __global__ __launch_bounds__(256) void head_count_kernel(const uint32_t *hcnt, const uint8_t *hmark, uint64_t n,
                                                          uint32_t *ecnt) {
     __shared__ uint32_t ws[4];
-    const uint64_t r0 = (uint64_t)blockIdx.x * EMIT_RPB + 4 * threadIdx.x;
+    static_assert(EMIT_RPB % 256 == 0, "the emit workgroup's rounds");
+    const uint64_t rb = (uint64_t)blockIdx.x * EMIT_RPB, end = min(n, rb + EMIT_RPB);
     uint32_t c = 0;
-    if (hmark) {                                 // (the bucket routes: a byte per rank)
-        if (r0 + 4 <= n) {
-            const uint32_t v = *(const uint32_t *)(hmark + r0);
-            c = ((v & 0xFFu) != 0) + ((v & 0xFF00u) != 0) + ((v & 0xFF0000u) != 0) + ((v & 0xFF000000u) != 0);
+#pragma unroll
+    for (uint32_t p = 0; p < EMIT_RPB; p += 1024) {   // four ranks per thread and pass
+        const uint64_t r0 = rb + p + 4 * threadIdx.x;
+        if (hmark) {                             // (the bucket routes: a byte per rank)
+            if (r0 + 4 <= end) {
+                const uint32_t v = *(const uint32_t *)(hmark + r0);
+                c += ((v & 0xFFu) != 0) + ((v & 0xFF00u) != 0) + ((v & 0xFF0000u) != 0) + ((v & 0xFF000000u) != 0);
+            } else {
+                for (uint64_t r = r0; r < end; ++r) c += hmark[r] != 0;
+            }
+        } else if (r0 + 4 <= end) {
+            const uint4 v = *(const uint4 *)(hcnt + r0);
+            c += (v.x != 0) + (v.y != 0) + (v.z != 0) + (v.w != 0);
         } else {
-            for (uint64_t r = r0; r < n; ++r) c += hmark[r] != 0;
+            for (uint64_t r = r0; r < end; ++r) c += hcnt[r] != 0;
         }
-    } else if (r0 + 4 <= n) {
-        const uint4 v = *(const uint4 *)(hcnt + r0);
-        c = (v.x != 0) + (v.y != 0) + (v.z != 0) + (v.w != 0);
-    } else {
-        for (uint64_t r = r0; r < n; ++r) c += hcnt[r] != 0;
     }
     c = wave_incl_sum(c);
     if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = c;
@@ -2983,7 +3017,27 @@ __global__ __launch_bounds__(256) void head_count_kernel(const uint32_t *hcnt, c
 // ballot / mbcnt inside the workgroup.  Entry: decoded key (P + suffix,
 // 'ACGT' from the 2-bit code, first base most significant), count,
 // first-occurrence order -- or the packed (code, {first, count}) pair for a
-// partial result.
+// partial result.  DEF: the default shape compiled in -- k = 16, |P| = 5,
+// narrow keys by rank (rkey32; no hrec, no high words), not partial: the 16
+// key bytes are P and three words of four bases each, formed without a loop.
+
+// four 2-bit codes (x: bits 7..0, the first base in bits 7..6) -> their four
+// 'ACGT' bytes, the first base in byte 0
+__device__ __forceinline__ uint32_t acgt4(uint32_t x) {
+    x = (x | (x << 12)) & 0x000F000Fu;           // bits 3..0 | bits 7..4 in the halves
+    x = (x | (x << 6)) & 0x03030303u;            // one code per byte, the last base in byte 0
+    return __builtin_bswap32(__builtin_amdgcn_perm(0u, 0x54474341u, x));   // ('A' 'C' 'G' 'T' picked by the bytes)
+}
+
+// bits sh + 7 .. sh of a key of two words (sh even, <= 120; uniform)
+__device__ __forceinline__ uint32_t key_bits8(uint64_t key, uint64_t keyh, uint32_t sh) {
+    if (sh >= 64) return (uint32_t)(keyh >> (sh - 64)) & 0xFFu;
+    uint64_t v = key >> sh;
+    if (sh > 56) v |= keyh << (64 - sh);
+    return (uint32_t)v & 0xFFu;
+}
+
+template <bool DEF>
 __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
     // decoded keys of a round's heads, staged so that the round's output
     // range [o0 * k, oend * k) is written with coalesced dword stores
@@ -2992,8 +3046,9 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
     __shared__ uint64_t s_pre;
     __shared__ uint32_t s_wp[4];
     const uint64_t n = a.n;
-    const uint32_t k = a.k, plen = a.plen;
-    const bool staged = !a.partial && (k & 3);     // else: aligned direct stores
+    const uint32_t k = DEF ? 16u : a.k, plen = DEF ? 5u : a.plen;
+    const bool partial = DEF ? false : a.partial != 0;
+    const bool staged = !partial && (k & 3);       // else: aligned direct stores
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint64_t rb = (uint64_t)blockIdx.x * EMIT_RPB;
     constexpr int NR = EMIT_RPB / 256;
@@ -3013,7 +3068,13 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
     for (int i = 0; i < NR; ++i) {
         const uint64_t r = rb + 256 * i + tid;
         ekey[i] = ecnt[i] = efirst[i] = ekeyh[i] = 0;
-        if (hcr[i]) {
+        if (DEF) {
+            if (hcr[i]) {
+                ekey[i] = a.rkey32[r];
+                ecnt[i] = hcr[i];
+                efirst[i] = a.rord[r];
+            }
+        } else if (hcr[i]) {
             if (a.hrec) {
                 const HeadRec v = a.hrec[r];
                 ekey[i] = v.key;
@@ -3067,7 +3128,16 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
         const uint64_t o = o64;
         if (f) {
             const uint64_t key = ekey[i], cnt = ecnt[i], keyh = ekeyh[i], first = efirst[i];
-            if (a.partial) {
+            if (DEF) {
+                a.cnt_out[o] = cnt;
+                a.first_out[o] = first;
+                uint32_t p0, p1;                 // (P[0..3], P[4]: uniform)
+                memcpy(&p0, a.P, 4);
+                memcpy(&p1, a.P + 4, 4);
+                const uint32_t c = (uint32_t)key;           // 11 bases: bits 21..0
+                const uint32_t w1 = (acgt4((c >> 16) & 0x3Fu) & 0xFFFFFF00u) | (p1 & 0xFFu);
+                *(uint4 *)(a.keys_out + o * 16) = make_uint4(p0, w1, acgt4((c >> 8) & 0xFFu), acgt4(c & 0xFFu));
+            } else if (partial) {
                 a.ukey[o] = key;
                 Agg v;
                 v.first = first;
@@ -3084,18 +3154,22 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs a) {
                 for (int w = 0; w < KMAX_TILE / 4; ++w) {
                     if ((uint32_t)w >= nw) break;
                     uint32_t v = 0;
+                    if (4 * (uint32_t)w >= plen && 4 * (uint32_t)w + 4 <= k) {   // (uniform) four bases of the key
+                        v = acgt4(key_bits8(key, keyh, 2 * (k - 4 - 4 * (uint32_t)w)));
+                    } else {                     // a word with prefix bytes, or the last one of a k that is no multiple of 4
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t pos = 4 * w + j;
-                        uint32_t ch = 0;
-                        if (pos < plen) {
-                            ch = a.P[pos];
-                        } else if (pos < k) {
-                            const uint32_t sh = 2 * (k - 1 - pos);      // (< 128)
-                            const uint32_t b = (uint32_t)(sh < 64 ? key >> sh : keyh >> (sh - 64)) & 3u;
-                            ch = (0x54474341u >> (8 * b)) & 0xFFu;
+                        for (int j = 0; j < 4; ++j) {
+                            const uint32_t pos = 4 * w + j;
+                            uint32_t ch = 0;
+                            if (pos < plen) {
+                                ch = a.P[pos];
+                            } else if (pos < k) {
+                                const uint32_t sh = 2 * (k - 1 - pos);      // (< 128)
+                                const uint32_t b = (uint32_t)(sh < 64 ? key >> sh : keyh >> (sh - 64)) & 3u;
+                                ch = (0x54474341u >> (8 * b)) & 0xFFu;
+                            }
+                            v |= ch << (8 * j);
                         }
-                        v |= ch << (8 * j);
                     }
                     if (k == 16) {                     // one 16-byte store
                         if (w == 0) w0 = v;
@@ -3417,8 +3491,12 @@ hipError_t launch_scan_tiles(const ScanArgs &a, hipStream_t s) {
 
 hipError_t launch_hits(const HitArgs &a, hipStream_t s) {
     const dim3 grid((a.n_tiles + 4 * HTPW - 1) / (4 * HTPW));
-    if (a.wide) hipLaunchKernelGGL(hit_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(hit_kernel<false>, grid, dim3(256), 0, s, a);
+    // the default shape, compiled in (a context moved to PBITS_LONG, or any
+    // other k, prefix length or key width, takes the run-time form)
+    const bool def = a.k == 16 && a.plen == 5 && a.packed && a.rkey32 && !a.wide && a.pbits == PBITS_DEFAULT;
+    if (def) hipLaunchKernelGGL((hit_kernel<false, true>), grid, dim3(256), 0, s, a);
+    else if (a.wide) hipLaunchKernelGGL((hit_kernel<true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((hit_kernel<false, false>), grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(hit_overflow_kernel, dim3(64), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -3707,7 +3785,13 @@ hipError_t launch_head_count(const uint32_t *hcnt, const uint8_t *hmark, uint64_
     return hipGetLastError();
 }
 hipError_t launch_emit(const EmitArgs &a, hipStream_t s) {
-    if (a.n) hipLaunchKernelGGL(emit_kernel, dim3((uint32_t)emit_blocks(a.n)), dim3(256), 0, s, a);
+    if (!a.n) return hipGetLastError();
+    const dim3 g((uint32_t)emit_blocks(a.n));
+    // the default shape, compiled in; partial, merged (hrec), wider-key and
+    // every other k / prefix length take the run-time form
+    const bool def = a.k == 16 && a.plen == 5 && !a.partial && !a.hrec && a.rkey32 && !a.rkeyh;
+    if (def) hipLaunchKernelGGL(emit_kernel<true>, g, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(emit_kernel<false>, g, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_merge_prep(const uint64_t *keys, const Agg *vals, uint64_t n, uint64_t *rkey, uint32_t *rkey32,

@@ -23,11 +23,16 @@ agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(out + "/pmc*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r.get("Kernel_Name", "")
-        if "scan_planes" not in k and "hit_kernel" not in k:
+        if "scan_planes" not in k and "hit_kernel" not in k and "::emit_kernel" not in k:
             continue
         agg[k.split("(")[0][-40:]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, d in agg.items():
     print(k)
+    mean = {c: sum(v) / max(1, len(v)) for c, v in d.items()}
     for c, v in sorted(d.items()):
-        print("  %-24s %.4g (per dispatch, %d samples)" % (c, sum(v) / max(1, len(v)) * (len(v) / max(1, len(set(v))) if False else 1), len(v)))
+        print("  %-24s %.4g (per dispatch, %d samples)" % (c, mean[c], len(v)))
+    if mean.get("SQ_WAVES"):                     # (the second pass has no wave count: divide by the first's)
+        for c in sorted(mean):
+            if c.startswith("SQ_") and c != "SQ_WAVES":
+                print("  %-24s %.1f per wave" % (c, mean[c] / mean["SQ_WAVES"]))
 PY
