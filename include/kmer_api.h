@@ -96,7 +96,11 @@ enum {
     KMER_FLAG_TABLE_FIXED_TEST = 1u << 17,
     /* debug: the general path's first merge attempt reports a hash collision,
      * so the two-hash (h2, h1) retry runs (exercises the collision route) */
-    KMER_FLAG_GEN_COLLIDE_TEST = 1u << 18
+    KMER_FLAG_GEN_COLLIDE_TEST = 1u << 18,
+    /* debug: the dense-hit path gives every wave 19 consecutive sequence lines
+     * at any chunk size (default: ceil(lines / 2^17), i.e. 1 up to 131,072
+     * lines per chunk) */
+    KMER_FLAG_DENSE_LPW_TEST = 1u << 19
 };
 
 typedef struct {
@@ -569,6 +573,13 @@ kmer_status kmer_table_digest(kmer_ctx *ctx, uint64_t *digest);
  * workload took. */
 kmer_status kmer_table_routes(kmer_ctx *ctx, uint64_t *p1_fixed, uint64_t *p1_merged, uint64_t *p1_counted,
                               uint64_t *p2_fixed);
+/* Diagnostics of the dense-hit path (a 1-3-base A/C/G/T prefix, step 1,
+ * k <= 64) since the last reset: the chunks that went through it and the
+ * largest number of consecutive sequence lines a wave was given in any of
+ * them (0 when there was none).  Either pointer may be NULL.  A context on
+ * another path answers KMER_OK with zeros; a group context KMER_E_STATE.  Lets
+ * a test assert that its waves took several lines. */
+kmer_status kmer_dense_routes(kmer_ctx *ctx, uint64_t *chunks, uint64_t *lines_per_wave);
 /* Table mode across ranks (replaces the one Map.set stream of lib/kmers.js:95
  * when the count is sharded over GPUs; reads are independent, :151-155).
  * Rank o (of `world` <= 1024) owns the pass-1 partitions [o*1024/world,

@@ -23,6 +23,7 @@ FLAG_LONG_LINES = 128
 FLAG_FASTA = 1 << 16      # FASTA records (an extension; kmer_api.h)
 FLAG_TABLE_FIXED_TEST = 1 << 17   # debug: table pass 1 always with fixed runs
 FLAG_GEN_COLLIDE_TEST = 1 << 18   # debug: general-path merge takes the collision retry
+FLAG_DENSE_LPW_TEST = 1 << 19     # debug: the dense-hit path gives every wave 19 sequence lines
 TAB_PARTS = 1024    # table mode: pass-1 partitions (ownership unit across ranks)
 # kmer_table_spectrum (include/kmer_api.h, KMER_SPECTRUM_*): values up to REG_MAX are kept in
 # registers, values below LDS_BINS in LDS; nbins is at most MAX_BINS
@@ -57,6 +58,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_result_arrays", "kmer_result_firsts", "kmer_result_write", "kmer_result_free",
            "kmer_synth_fastq_device",
            "kmer_last_timing", "kmer_phase_times", "kmer_table_stats", "kmer_table_digest", "kmer_table_routes", "kmer_table_device",
+           "kmer_dense_routes",
            "kmer_table_exchange_prepare", "kmer_table_finish_exchanged",
            "kmer_table_lookup", "kmer_table_lookup_device",
            "kmer_table_screen_device", "kmer_table_screen",
@@ -176,6 +178,7 @@ def _load():
         "kmer_table_stats": (ctypes.c_int, [vp, pu64, pu64, pu64]),
         "kmer_table_digest": (ctypes.c_int, [vp, pu64]),
         "kmer_table_routes": (ctypes.c_int, [vp, pu64, pu64, pu64, pu64]),
+        "kmer_dense_routes": (ctypes.c_int, [vp, pu64, pu64]),
         "kmer_table_device": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                              ctypes.POINTER(vp), pu64]),
         "kmer_table_exchange_prepare": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(vp), pu64, pu64]),
@@ -463,6 +466,13 @@ class Counter:
         self._check(LIB.kmer_table_routes(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)),
                     "table_routes")
         return {"fixed": a.value, "merged": b.value, "counted": c.value, "p2_fixed": d.value}
+
+    def dense_routes(self):
+        """Dense-hit path since the last reset: its chunks, and the largest number of consecutive
+        sequence lines a wave was given (0: no chunk went through it)."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(LIB.kmer_dense_routes(self.h, ctypes.byref(a), ctypes.byref(b)), "dense_routes")
+        return {"chunks": a.value, "lines_per_wave": b.value}
 
     def table_device(self):
         """Table mode: (d_entries, d_bucket_start, d_bucket_len, d_big, n_big) in device memory."""

@@ -1321,6 +1321,14 @@ kmer_status kmer_table_routes(kmer_ctx *c, uint64_t *p1_fixed, uint64_t *p1_merg
     return KMER_OK;
 }
 
+kmer_status kmer_dense_routes(kmer_ctx *c, uint64_t *chunks, uint64_t *lines_per_wave) {
+    if (!c) return KMER_E_BAD_PARAM;
+    SETTLE(c);
+    if (chunks) *chunks = c->d_chunks;
+    if (lines_per_wave) *lines_per_wave = c->d_lpw;
+    return KMER_OK;
+}
+
 // ---- table spectrum and extraction (kmer_abundance.hip) ----
 static_assert(KMER_SPECTRUM_REG_MAX == AB_REGS && KMER_SPECTRUM_LDS_BINS == AB_LDS_BINS &&
                   KMER_SPECTRUM_MAX_BINS == AB_HIST_BINS,

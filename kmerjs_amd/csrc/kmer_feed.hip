@@ -701,6 +701,9 @@ kmer_status dense_windows_feed(kmer_ctx *c, const uint8_t *d, uint64_t len, uint
     g.lines = c->lines.p;
     g.n_lines = n_seq;
     g.lpw = std::max<uint64_t>(1, (n_seq + (1u << 17) - 1) >> 17);   // (<= 128 K waves)
+    if (c->p.flags & KMER_FLAG_DENSE_LPW_TEST) g.lpw = 19;           // (two fetches per share, at any size: the tests)
+    c->d_chunks += 1;
+    c->d_lpw = std::max(c->d_lpw, g.lpw);
     g.k = c->p.k;
     g.plen = (uint32_t)c->prefix.size();
     g.pbits = c->pbits;
@@ -992,6 +995,7 @@ kmer_status reset(kmer_ctx *c) {
     c->win_slots = false;
     c->t_p1_fixed = c->t_p1_merged = c->t_p1_counted = 0;
     c->t_p2_fixed = 0;
+    c->d_chunks = c->d_lpw = 0;
     c->gm_n = 0;
     c->gm_last = 0;
     c->gm_merged = true;

@@ -54,7 +54,8 @@
 using namespace kmerhip;
 
 // every KMER_FLAG_* of include/kmer_api.h
-constexpr uint32_t KMER_FLAGS_PUBLIC = 0xFFu | KMER_FLAG_FASTA | KMER_FLAG_TABLE_FIXED_TEST | KMER_FLAG_GEN_COLLIDE_TEST;
+constexpr uint32_t KMER_FLAGS_PUBLIC = 0xFFu | KMER_FLAG_FASTA | KMER_FLAG_TABLE_FIXED_TEST | KMER_FLAG_GEN_COLLIDE_TEST |
+                                     KMER_FLAG_DENSE_LPW_TEST;
 
 namespace kmerhip {
 
@@ -266,6 +267,7 @@ struct kmer_ctx {
     uint64_t t_keys = 0;           // pass-1 slots of the session (keys, plus filler of fixed runs)
     uint64_t t_p1_fixed = 0, t_p1_merged = 0, t_p1_counted = 0;   // pass-1 routes (kmer_table_routes)
     uint64_t t_p2_fixed = 0;       // finishes whose pass 2 ran with fixed bucket capacities (tab_scatter2f)
+    uint64_t d_chunks = 0, d_lpw = 0;   // dense-hit path: its chunks, the largest lines per wave (kmer_dense_routes)
     uint64_t t_fill = 0;           // ... of which filler slots (an estimate: windows with non-ACGT bytes are not keys)
     std::vector<uint64_t> t_cbase; // per chunk: first key in tb1
     std::vector<std::vector<uint64_t>> t_coff;   // per chunk: TAB_NB + 1 partition starts (chunk-relative)
