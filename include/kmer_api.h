@@ -523,7 +523,50 @@ kmer_status kmer_table_extract(kmer_ctx *ctx, uint64_t lo, uint64_t hi, kmer_res
  * k, KMER_FLAG_CANONICAL or prefix bytes; KMER_E_STATE for a group context
  * (ndev > 1), a context not in table mode, or one without a table finish.
  * KMER_E_DEVICE, naming the bucket and the context, if a bucket's extent lies
- * past its table (it is not read). */
+ * past its table (it is not read).
+ *
+ * kmer_table_setop_into: the same operation (a, b, op, min_a, min_b exactly as
+ * above, a == b legal) with a table as its result, so that operations chain,
+ * counts of separate sessions merge (UNION, as `jellyfish merge`), and reads
+ * are screened or filtered against "A minus B".  dst is a third context:
+ * single-device, in table mode, on the same device, equal to a in k,
+ * KMER_FLAG_CANONICAL and prefix bytes, in any session state (a chunk in
+ * flight is settled, then dst is reset as by kmer_reset).  After KMER_OK dst
+ * is in the state a table finish leaves, until its next reset: stats, digest,
+ * lookup, spectrum, extract, screen, filter, kmer_table_device,
+ * kmer_match_open_table, compare and the setops (dst as a, b or, in a later
+ * call, dst again) work on it.  The Map dst describes -- the one its lookup
+ * answers for and kmer_table_extract(dst, 1, 0) lists -- equals row for row
+ * the host result of kmer_table_setop(a, b, op, min_a, min_b): the record keys
+ * of a and b, joined on the host by the same rules, become dst's records;
+ * kmer_lines(dst) is a's.  kmer_table_stats(dst) and kmer_table_digest(dst)
+ * are those of a count that produced this Map; with thresholds 1,
+ * digest(UNION) = digest(a) + digest(b) mod 2^64, and the UNION of the tables
+ * of inputs X and Y has the stats, digest and lookup answers of one count
+ * over X followed by Y.  The operation on the Map values is the operation on
+ * the class counts (both sides double a self-complementary key alike), the
+ * threshold tested on the Map value; a class without a Map key (canonical
+ * mode, a prefix only its larger string starts with) has its class count for
+ * a value.  The result's entry is remainder << 20 | min(C, 0xFFFFF); a count C
+ * >= 0xFFFFF -- a UNION can make one from two small ones -- goes to dst's big
+ * list; a result of 0 is no entry.  Bucket q of the result is written
+ * straight from the join of bucket q of a and b (entries per bucket counted,
+ * scanned, then written; the order within a bucket is unspecified): no sort
+ * and no decode to key bytes, and dst's entries, bucket index and big list are
+ * allocated exactly.  a and b are left unchanged: table, bucket index, big
+ * list, records, kmer_lines, and (unlike kmer_table_setop_device) a's extract
+ * buffers.  Exchanged a and b (same world and rank) give dst that rank's
+ * share: the ranks' stats and digests of dst add up.
+ * The work runs on dst's stream, which waits for the work queued on a's and
+ * b's; the call is complete on return, and none of the three contexts may be
+ * in use on another thread.  Checked before any device call: KMER_E_BAD_PARAM
+ * for a NULL context, op > KMER_SETOP_UNION, dst == a or dst == b (no in-place
+ * operation), contexts on different devices, dst or b differing from a in k,
+ * KMER_FLAG_CANONICAL or prefix bytes; KMER_E_STATE for a group context among
+ * the three, a or b not in table mode or without a table finish, dst not in
+ * table mode.  During the call: KMER_E_OOM leaves all three contexts usable,
+ * dst in its reset state; KMER_E_DEVICE names the bucket and the context, as
+ * above.  The message of a failure is a's last error. */
 #define KMER_JOIN_TILE 1024u
 typedef struct {
     uint64_t keys_a, keys_b, keys_both;   /* distinct Map keys in A, in B, in both            */
@@ -537,6 +580,8 @@ kmer_status kmer_table_setop_device(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint6
                                     const void **d_keys, const void **d_counts, uint64_t *n);
 kmer_status kmer_table_setop(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
                              kmer_result **out);
+kmer_status kmer_table_setop_into(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
+                                  kmer_ctx *dst);
 /* The table itself, in device memory (to read counts, use kmer_table_lookup,
  * which owns the two key encodings below; this is the raw layout for a
  * consumer that walks the whole table; the library's own are

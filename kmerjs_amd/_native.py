@@ -64,7 +64,7 @@ EXPORTS = ["kmer_open", "kmer_close", "kmer_count_file", "kmer_count_buffer", "k
            "kmer_table_screen_device", "kmer_table_screen",
            "kmer_table_filter_device", "kmer_table_filter",
            "kmer_table_spectrum", "kmer_table_extract_device", "kmer_table_extract",
-           "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop",
+           "kmer_table_compare", "kmer_table_setop_device", "kmer_table_setop", "kmer_table_setop_into",
            "kmer_status_string", "kmer_last_error", "kmer_version"]
 # include/kmer_match.h (the template matcher, same library)
 MATCH_EXPORTS = ["kmer_db_open", "kmer_db_open_fasta_device", "kmer_db_open_fasta", "kmer_db_template_stats",
@@ -201,6 +201,7 @@ def _load():
         "kmer_table_setop_device": (ctypes.c_int, [vp, vp, ctypes.c_uint32, u64, u64, ctypes.POINTER(vp),
                                                    ctypes.POINTER(vp), pu64]),
         "kmer_table_setop": (ctypes.c_int, [vp, vp, ctypes.c_uint32, u64, u64, ctypes.POINTER(vp)]),
+        "kmer_table_setop_into": (ctypes.c_int, [vp, vp, ctypes.c_uint32, u64, u64, vp]),
         "kmer_status_string": (ctypes.c_char_p, [ctypes.c_int]),
         "kmer_last_error": (ctypes.c_char_p, [vp]),
         "kmer_version": (ctypes.c_char_p, []),
@@ -636,6 +637,16 @@ class Counter:
         r = ctypes.c_void_p()
         self._check(LIB.kmer_table_setop(self.h, other.h, op, min_a, min_b, ctypes.byref(r)), "table_setop")
         return Result(r)
+
+    def table_setop_into(self, other, op, dst, min_a=1, min_b=1):
+        """The set operation with a table as its result: `dst` (a third
+        table-mode Counter of the same k, mode, prefix and device, in any
+        session state; it is reset) is left as a table finish leaves it,
+        holding the Map that table_setop(other, op, min_a, min_b) returns,
+        record keys included.  Returns dst's (canonical, keys, total).  This
+        table and `other`'s are unchanged."""
+        self._check(LIB.kmer_table_setop_into(self.h, other.h, op, min_a, min_b, dst.h), "table_setop_into")
+        return dst.table_stats()
 
     def table_exchange_prepare(self, world):
         """Table mode across ranks: (d_send, counts, parts) -- this session's

@@ -1798,6 +1798,27 @@ static kmer_status setop_run(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min
     return KMER_OK;
 }
 
+// the record keys of the two contexts, joined by the setop's rules: (key, value), in no order
+static std::vector<std::pair<std::string, uint64_t>> setop_records(const kmer_ctx *a, const kmer_ctx *b, uint32_t op,
+                                                                   uint64_t min_a, uint64_t min_b) {
+    const auto ra = join_records(a, min_a), rb = join_records(b, min_b);
+    std::vector<std::pair<std::string, uint64_t>> recs;
+    for (auto &kv : ra) {
+        const auto it = rb.find(kv.first);
+        if (op == KMER_SETOP_INTERSECT) {
+            if (it != rb.end()) recs.emplace_back(kv.first, std::min(kv.second, it->second));
+        } else if (op == KMER_SETOP_SUBTRACT) {
+            if (it == rb.end()) recs.push_back(kv);
+        } else {
+            recs.emplace_back(kv.first, kv.second + (it != rb.end() ? it->second : 0));
+        }
+    }
+    if (op == KMER_SETOP_UNION)
+        for (auto &kv : rb)
+            if (!ra.count(kv.first)) recs.push_back(kv);
+    return recs;
+}
+
 kmer_status kmer_table_setop_device(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b,
                                     const void **d_keys, const void **d_counts, uint64_t *n) {
     if (!a || !b || !d_keys || !d_counts || !n || op > KMER_SETOP_UNION) return KMER_E_BAD_PARAM;
@@ -1829,22 +1850,7 @@ kmer_status kmer_table_setop(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min
         HIPCHK(a, hipMemcpyAsync(cnt.data(), dc, n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(a, hipStreamSynchronize(s));
     }
-    // the record keys of the two contexts, joined by the same rules
-    const auto ra = join_records(a, min_a), rb = join_records(b, min_b);
-    std::vector<std::pair<std::string, uint64_t>> recs, rows;
-    for (auto &kv : ra) {
-        const auto it = rb.find(kv.first);
-        if (op == KMER_SETOP_INTERSECT) {
-            if (it != rb.end()) recs.emplace_back(kv.first, std::min(kv.second, it->second));
-        } else if (op == KMER_SETOP_SUBTRACT) {
-            if (it == rb.end()) recs.push_back(kv);
-        } else {
-            recs.emplace_back(kv.first, kv.second + (it != rb.end() ? it->second : 0));
-        }
-    }
-    if (op == KMER_SETOP_UNION)
-        for (auto &kv : rb)
-            if (!ra.count(kv.first)) recs.push_back(kv);
+    std::vector<std::pair<std::string, uint64_t>> recs = setop_records(a, b, op, min_a, min_b), rows;
     merge_rows(kb, cnt, k, recs, rows);
     StreamPos pos;
     st = read_pos(a, &pos);
@@ -1859,6 +1865,164 @@ kmer_status kmer_table_setop(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min
         r->firsts.push_back(0);
     }
     *out = r;
+    return KMER_OK;
+}
+
+// The set operation whose result stays a table: the device part, on dst's
+// stream and scratch (errors are left on dst; the caller reports them on a).
+// dst has been reset; nothing of it is committed before the last check, so a
+// failure leaves it in its reset state.  Count per bucket, scan, exact
+// allocation, write -- no sort and no decode.
+static kmer_status setop_into_run(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b, kmer_ctx *dst,
+                                  TabJoin &j) {
+    hipStream_t s = dst->stream;
+    bool ok = dst->tjoin.ensure(16, s) == hipSuccess && dst->tlk_bad.ensure(2, s) == hipSuccess &&
+              dst->tnd.ensure(TAB_NQ + 1, s) == hipSuccess && dst->tstart.ensure(TAB_NQ + 1, s) == hipSuccess &&
+              dst->tstats.ensure(5, s) == hipSuccess && dst->tbig.ensure(1 << 16, s) == hipSuccess &&
+              (op != JOIN_UNION || dst->tH.ensure(TAB_NQ, s) == hipSuccess);
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(dst, KMER_E_OOM, "device allocation failed (the result table's bucket index)");
+    }
+    // dst's stream after the work queued on a's and on b's
+    HIPCHK(dst, hipEventRecord(dst->evw, a->stream));
+    HIPCHK(dst, hipStreamWaitEvent(s, dst->evw, 0));
+    if (b != a) {
+        HIPCHK(dst, hipEventRecord(dst->evw, b->stream));
+        HIPCHK(dst, hipStreamWaitEvent(s, dst->evw, 0));
+    }
+    const uint32_t walks = op == JOIN_UNION ? 2u : 1u;           // UNION: A's classes, then B's that are not in A
+    j.min_a = std::max<uint64_t>(min_a, 1);
+    j.min_b = std::max<uint64_t>(min_b, 1);
+    j.op = op;
+    j.n_out = dst->tjoin.p + 8;
+    j.err = dst->d_err;
+    j.badq = dst->tlk_bad.p;
+    j.nd_dst = dst->tnd.p;
+    j.cur_dst = op == JOIN_UNION ? dst->tH.p : nullptr;
+    auto errors = [&](uint32_t e, const uint32_t bad[2]) -> kmer_status {
+        if (!(e & (ERR_TAB_LOOKUP | ERR_TAB_EXTRACT))) return KMER_OK;
+        HIPCHK(dst, hipMemsetD32Async((hipDeviceptr_t)dst->d_err, (int)(e & ~(ERR_TAB_LOOKUP | ERR_TAB_EXTRACT)), 1, s));
+        HIPCHK(dst, hipStreamSynchronize(s));
+        if (e & ERR_TAB_LOOKUP)
+            return fail(dst, KMER_E_DEVICE, "table setop into: the extent of bucket " + std::to_string(bad[0]) + " of the " +
+                                                (bad[1] ? "second" : "first") + " context lies past the table");
+        return fail(dst, KMER_E_DEVICE, "table setop into: more entries written than counted");
+    };
+    uint64_t total = 0, nbig = 0;
+    uint32_t e = 0, bad[2] = {0, 0};
+    HIPCHK(dst, hipMemsetAsync(j.n_out, 0, 8, s));
+    HIPCHK(dst, hipMemsetAsync(dst->tnd.p + TAB_NQ, 0, sizeof(uint32_t), s));   // (the scan's last input)
+    for (j.second = 0; j.second < walks; ++j.second) HIPCHK(dst, launch_tab_join_tcount(j, s));
+    ROCPRIM_RUN(dst, rocprim::exclusive_scan(t, b, dst->tnd.p, dst->tstart.p, (uint64_t)0, (size_t)(TAB_NQ + 1),
+                                             rocprim::plus<uint64_t>(), s));
+    HIPCHK(dst, hipMemcpyAsync(&total, dst->tstart.p + TAB_NQ, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(dst, hipMemcpyAsync(&nbig, j.n_out, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(dst, hipMemcpyAsync(&e, dst->d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(dst, hipMemcpyAsync(bad, j.badq, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(dst, hipStreamSynchronize(s));
+    kmer_status st = errors(e, bad);
+    if (st) return st;
+    uint64_t stats[3] = {0, 0, 0};
+    if (total) {
+        if (dst->tb1.ensure(total, s) != hipSuccess || dst->tbig.ensure(nbig, s) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(dst, KMER_E_OOM, "device allocation failed (" + std::to_string(total) + " entries of a set operation)");
+        }
+        j.start_dst = dst->tstart.p;
+        j.ent_dst = dst->tb1.p;
+        j.cap_dst = total;
+        j.big_dst = dst->tbig.p;
+        j.big_cap = nbig;
+        j.stats = dst->tstats.p;
+        uint64_t wrote_big = 0;
+        HIPCHK(dst, hipMemsetAsync(j.n_out, 0, 8, s));
+        HIPCHK(dst, hipMemsetAsync(j.stats, 0, 3 * sizeof(unsigned long long), s));
+        for (j.second = 0; j.second < walks; ++j.second) HIPCHK(dst, launch_tab_join_twrite(j, s));
+        HIPCHK(dst, hipMemcpyAsync(stats, j.stats, sizeof(stats), hipMemcpyDeviceToHost, s));
+        HIPCHK(dst, hipMemcpyAsync(&wrote_big, j.n_out, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(dst, hipMemcpyAsync(&e, dst->d_err, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(dst, hipMemcpyAsync(bad, j.badq, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(dst, hipStreamSynchronize(s));
+        st = errors(e, bad);
+        if (st) return st;
+        if (stats[0] != total || wrote_big != nbig)
+            return fail(dst, KMER_E_DEVICE, "table setop into: counted and written entries differ");
+    }
+    // the state a table finish leaves
+    dst->t_ent = total ? dst->tb1.p : nullptr;
+    dst->t_keys = total;
+    dst->t_canon = stats[0];
+    dst->t_nkeys = stats[1];
+    dst->t_sum = stats[2];
+    dst->t_nbig = total ? nbig : 0;
+    dst->n_out = dst->t_nkeys;
+    return KMER_OK;
+}
+
+kmer_status kmer_table_setop_into(kmer_ctx *a, kmer_ctx *b, uint32_t op, uint64_t min_a, uint64_t min_b, kmer_ctx *dst) {
+    if (!a || !b || !dst || op > KMER_SETOP_UNION || dst == a || dst == b) return KMER_E_BAD_PARAM;
+    // parameters, then states: no device call yet
+    for (kmer_ctx *c : {b, dst}) {
+        const char *who = c == dst ? "result" : "second";
+        if (c->device != a->device)
+            return fail(a, KMER_E_BAD_PARAM, std::string("the ") + who + " context is on another device than the first");
+        if (c->p.k != a->p.k || ((c->p.flags ^ a->p.flags) & KMER_FLAG_CANONICAL) || c->prefix != a->prefix)
+            return fail(a, KMER_E_BAD_PARAM,
+                        std::string("the ") + who + " context differs from the first in k, KMER_FLAG_CANONICAL or prefix");
+    }
+    for (kmer_ctx *c : {a, b, dst}) {
+        const char *who = c == dst ? "result" : c == a ? "first" : "second";
+        if (!c->group.empty()) return fail(a, KMER_E_STATE, std::string("single-device call: the ") + who + " context is a group");
+        if (c->mode != MODE_TABLE) return fail(a, KMER_E_STATE, std::string("the ") + who + " context is not in table mode");
+        if (c != dst && !c->t_done) return fail(a, KMER_E_STATE, std::string("no table finish yet on the ") + who + " context");
+    }
+    if (hipSetDevice(a->device) != hipSuccess) return fail(a, KMER_E_DEVICE, "hipSetDevice failed");
+    // both inputs settled, their views filled (an empty table: nd == nullptr)
+    TabJoin j;
+    memset(&j, 0, sizeof(j));
+    TabOwner oa, ob;
+    kmer_status st = table_view_impl(a, &j.a, &oa);
+    if (st) return st;
+    if (b != a) {
+        st = table_view_impl(b, &j.b, &ob);
+        if (st) return fail(a, st, "second context: " + b->err);
+    } else {
+        j.b = j.a;
+        ob = oa;
+    }
+    auto hollow = [](TabView *v, const TabView &from) {          // (the key parameters are the same on both sides)
+        *v = from;
+        v->ent = nullptr;
+        v->start = nullptr;
+        v->nd = nullptr;
+        v->big = nullptr;
+        v->n_big = 0;
+        v->cap = 0;
+    };
+    if (oa.empty && !ob.empty) hollow(&j.a, j.b);
+    if (ob.empty && !oa.empty) hollow(&j.b, j.a);
+    // what dst takes over from a, and the record keys joined on the host
+    StreamPos pos;
+    st = read_pos(a, &pos);
+    if (st) return st;
+    const uint64_t lines = a->fasta ? a->fa_lines : pos.lines + pos.ends_open;
+    const std::vector<std::pair<std::string, uint64_t>> recs = setop_records(a, b, op, min_a, min_b);
+    // dst: a chunk in flight settled, then the reset; its position is a's
+    st = reset(dst);
+    if (st) return fail(a, st, "result context: " + dst->err);
+    dst->t_canon = dst->t_nkeys = dst->t_sum = dst->t_nbig = 0;
+    dst->prep_flags |= PREP_SETPOS;
+    dst->prep_lines = lines;
+    dst->host_lines = lines;
+    if (dst->fasta) dst->fa_lines = lines;
+    st = flush_prep(dst, dst->stream, 0);                        // (clears dst's device error word as well)
+    if (!st && !(oa.empty && ob.empty)) st = setop_into_run(a, b, op, min_a, min_b, dst, j);
+    if (st) return fail(a, st, "result context: " + dst->err);
+    for (auto &kv : recs) dst->exotic.emplace(kv.first, Ent{kv.second, 0});
+    dst->t_nq = a->t_nq;
+    dst->t_done = true;
+    dst->open_stream = false;
     return KMER_OK;
 }
 

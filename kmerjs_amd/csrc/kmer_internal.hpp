@@ -1114,6 +1114,29 @@ __host__ __device__ inline uint32_t join_slot(uint64_t sig, uint32_t nslots) {
     return (uint32_t)((sig * TAB_MUL) >> 40) & (nslots - 1);
 }
 enum { JOIN_INTERSECT = 0, JOIN_SUBTRACT = 1, JOIN_UNION = 2 };   // (KMER_SETOP_*)
+// The result as a table (kmer_table_setop_into): the arithmetic of one class.
+// The Map value one walk gives a class with the values va / vb on the two
+// sides (0: not there); `second`: JOIN_UNION's second walk.  0: no result.
+__host__ __device__ inline uint64_t join_result(uint32_t op, bool second, uint64_t va, uint64_t vb, uint64_t min_a,
+                                                uint64_t min_b) {
+    const bool in_a = va >= min_a, in_b = vb >= min_b;
+    if (op == JOIN_INTERSECT) return in_a && in_b ? (va < vb ? va : vb) : 0;
+    if (op == JOIN_SUBTRACT) return in_a && !in_b ? va : 0;
+    if (!second) return in_a ? va + (in_b ? vb : 0) : 0;
+    return in_b && !in_a ? vb : 0;
+}
+// the class count C behind a result value: both sides double a
+// self-complementary class alike, so its value is even
+__host__ __device__ inline uint64_t join_class_count(uint64_t v, bool dbl) { return dbl ? v >> 1 : v; }
+// the result's entry of a class: rem << 20 | min(C, TAB_CMAX); *big: C goes to the big list as well
+__host__ __device__ inline uint64_t join_entry(uint64_t rem, uint64_t C, bool *big) {
+    *big = C >= TAB_CMAX;
+    return (rem << 20) | (C < TAB_CMAX ? C : TAB_CMAX);
+}
+// slot `off` of a result bucket of nd entries that begins at `start` in a table of cap entries: may it be written?
+__host__ __device__ inline bool join_slot_ok(uint64_t start, uint32_t off, uint32_t nd, uint64_t cap) {
+    return off < nd && start <= cap && off < cap - start;
+}
 struct TabJoin {
     TabView a, b;                  // nd == nullptr: an empty table; the key parameters (k, prefix, mode) are a's
     uint64_t min_a, min_b;         // a key is in a side iff its value there is >= this (>= 1)
@@ -1125,10 +1148,22 @@ struct TabJoin {
     uint64_t *codes, *vals;        // setop: (2-bit code, value) pairs, as the extract's
     unsigned int *err;             // ERR_TAB_LOOKUP / ERR_TAB_EXTRACT ...
     uint32_t *badq;                // ... [0] the bucket, [1] the side (0 a, 1 b)
+    // the result as a table (launch_tab_join_tcount / twrite).  n_out: the
+    // result entries with a count >= TAB_CMAX (count), the big list's cursor (write)
+    uint32_t *nd_dst;              // count: result entries of bucket q (stored; JOIN_UNION's second walk adds)
+    const uint64_t *start_dst;     // write: their exclusive scan (TAB_NQ + 1)
+    uint32_t *cur_dst;             // write, JOIN_UNION: the offset the first walk reached in bucket q
+    uint64_t *ent_dst;             // write: the result's entries ...
+    uint64_t cap_dst;              // ... as many as the scan's total
+    TabBig *big_dst;
+    uint64_t big_cap;
+    unsigned long long *stats;     // write: [0] classes [1] Map keys [2] sum of Map values
 };
 hipError_t launch_tab_join_compare(const TabJoin &j, hipStream_t s);
 hipError_t launch_tab_join_count(const TabJoin &j, hipStream_t s);
 hipError_t launch_tab_join_write(const TabJoin &j, hipStream_t s);
+hipError_t launch_tab_join_tcount(const TabJoin &j, hipStream_t s);
+hipError_t launch_tab_join_twrite(const TabJoin &j, hipStream_t s);
 // multi-GPU table exchange: copy n segments {src offset, dst offset, length}
 // of u64 keys (one workgroup per segment, grid-strided)
 struct TabSeg {

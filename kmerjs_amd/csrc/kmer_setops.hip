@@ -32,6 +32,20 @@
 // atomic per entry: compare keeps its eight sums in registers (one wave
 // reduction and one atomic per sum per wave at the end), count one sum, write
 // one returning atomic per round of a wave.
+//
+// The result as a table (kmer_table_setop_into; JM_TCOUNT / JM_TWRITE).  Buckets
+// are unsorted and remainders within one are distinct, so bucket q of the
+// result is written straight from the join of bucket q of A and B: no sort, no
+// decode to key bytes.  The count walk leaves nd_dst[q], a register of the
+// pair's lane (short pair) or a wave sum (long pair) stored once, UNION's
+// second walk adding to the first's; the host scans nd_dst into start_dst;
+// the write walk puts bucket q's entries (rem << 20 | min(C, TAB_CMAX)) at
+// start_dst[q] + a running offset: the lane's own (short pair), or the wave's
+// plus a DPP scan over the lanes that hold a result in the round (long pair),
+// carried across the ranges of a split bucket and, through cur_dst[q], across
+// UNION's two walks.  A slot at or past nd_dst[q] is refused.  Counts >=
+// TAB_CMAX go to the result's big list, one returning atomic per wave round
+// that has any; the statistics are summed in registers.
 #include "kmer_device.hpp"
 
 namespace kmerhip {
@@ -39,7 +53,8 @@ namespace kmerhip {
 constexpr uint32_t JOIN_UNROLL = 4;      // wave loads (64 entries, 512 B each) in flight per round
 constexpr uint32_t JOIN_GROUPS = TAB_NQ / 64;
 constexpr uint32_t JOIN_WAVES = 4;       // waves of a workgroup: 4 slices of 16 KiB, two workgroups per CU
-enum { JM_COMPARE = 0, JM_COUNT = 1, JM_WRITE = 2 };
+// (JM_TCOUNT / JM_TWRITE: the result as a table -- entries per bucket, then the entries themselves)
+enum { JM_COMPARE = 0, JM_COUNT = 1, JM_WRITE = 2, JM_TCOUNT = 3, JM_TWRITE = 4 };
 
 // LDS traffic of one wave's lanes to each other's slots: ordered here
 __device__ __forceinline__ void join_sync() {
@@ -94,6 +109,48 @@ __device__ __forceinline__ uint32_t join_visit(const TabJoin &j, bool p_is_a, ui
     else v = in_b && !in_a ? vb : 0;
     *val = v;
     return v ? n : 0u;
+}
+
+// The result as a table: one class seen from the probing side, ep its entry
+// there, es its entry on the staged side (0: none).  Returns the class count C
+// of the result's entry (0: no entry), *nk its Map keys and *v their value.
+// Both sides double a self-complementary class alike (tab_entry_keys), so the
+// operation on the Map values is the operation on the class counts, with the
+// thresholds tested on the Map value.  A class without a Map key (canonical
+// mode with a prefix that only the larger string starts with) has its class
+// count for a value: a count holds it, and so does a UNION.
+template <bool DECODE>
+__device__ __forceinline__ uint64_t join_class(const TabJoin &j, bool p_is_a, uint32_t q, uint64_t ep, uint64_t es,
+                                               uint32_t *nk, uint64_t *v) {
+    *nk = 0;
+    *v = 0;
+    if (!(ep & TAB_CMAX)) return 0;
+    const uint64_t h = ((uint64_t)q << TAB_RBITS) | (ep >> 20);
+    uint64_t keys[2];
+    bool dbl = false;
+    uint32_t n = j.a.canonical ? 1u : 2u;
+    if (DECODE) n = tab_entry_keys(h, j.a.k, j.a.plo, j.a.phi, j.a.pmask, j.a.canonical != 0, keys, &dbl);
+    const uint64_t vp = join_value(j, p_is_a, ep, h, dbl);
+    const uint64_t vs = es ? join_value(j, !p_is_a, es, h, dbl) : 0;
+    const uint64_t r = join_result(j.op, j.second != 0, p_is_a ? vp : vs, p_is_a ? vs : vp, j.min_a, j.min_b);
+    *nk = r ? n : 0u;
+    *v = r;
+    return join_class_count(r, dbl);
+}
+
+// the result as a table: one entry at slot `off` of its bucket (start sd, nd entries)
+__device__ __forceinline__ void join_put_entry(const TabJoin &j, uint64_t sd, uint32_t off, uint32_t nd, uint64_t word) {
+    if (join_slot_ok(sd, off, nd, j.cap_dst)) j.ent_dst[sd + off] = word;
+    else atomicOr(j.err, ERR_TAB_EXTRACT);                       // count and write passes disagree: a defect
+}
+
+__device__ __forceinline__ void join_put_big(const TabJoin &j, uint64_t slot, uint64_t h, uint64_t C) {
+    if (slot < j.big_cap) {
+        j.big_dst[slot].h = h;
+        j.big_dst[slot].count = C;
+    } else {
+        atomicOr(j.err, ERR_TAB_EXTRACT);
+    }
 }
 
 // compare: the staged side's own sums (its keys and their values)
@@ -175,6 +232,16 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
         const uint32_t len_a = join_extent(j, j.a, end_a, q, 0, &base_a);
         const uint32_t len_b = join_extent(j, j.b, end_b, q, 1, &base_b);
         const bool shortp = len_a <= JOIN_LANE_MAX && len_b <= JOIN_LANE_MAX;
+        // the result as a table: bucket q's entries so far (count), its extent and the offset reached (write)
+        uint32_t nd_q = 0, off_q = 0;
+        uint64_t sd_q = 0;
+        if (MODE == JM_TCOUNT) nd_q = j.second ? j.nd_dst[q] : 0u;
+        if (MODE == JM_TWRITE) {
+            nd_q = j.nd_dst[q];
+            sd_q = j.start_dst[q];
+            off_q = j.second ? j.cur_dst[q] : 0u;
+        }
+        const bool carry = MODE == JM_TWRITE && j.op == JOIN_UNION && !j.second;   // the second walk goes on from here
         {   // lane-per-pair: no cross-lane reads inside the loops
             const uint64_t *ent_p = swap ? j.b.ent : j.a.ent, *ent_s = swap ? j.a.ent : j.b.ent;
             const uint64_t bp = swap ? base_b : base_a, bs = swap ? base_a : base_b;
@@ -191,7 +258,7 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                     const uint64_t ep = ent_p[bp + i];
                     mine += join_visit<MODE, DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), acc, keys, &v);
                 }
-            } else {
+            } else if (MODE == JM_WRITE) {
                 uint32_t t = 0;
                 for (uint32_t i = 0; i < lp; ++i) {
                     const uint64_t ep = ent_p[bp + i];
@@ -202,6 +269,36 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                     const uint64_t ep = ent_p[bp + i];
                     const uint32_t n = join_visit<MODE, DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), acc, keys, &v);
                     for (uint32_t x = 0; x < n; ++x) join_put(j, slot++, keys[x], v);
+                }
+            } else if (MODE == JM_TCOUNT) {                      // the bucket's count: a register, stored once
+                uint32_t c = 0, nk;
+                for (uint32_t i = 0; i < lp; ++i) {
+                    const uint64_t ep = ent_p[bp + i];
+                    const uint64_t C = join_class<DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), &nk, &v);
+                    c += C != 0;
+                    mine += C >= TAB_CMAX;
+                }
+                if (shortp) j.nd_dst[q] = nd_q + c;
+            } else {                                             // JM_TWRITE: the entries in bucket order of P
+                uint32_t off = off_q, nb = 0, nk;
+                for (uint32_t i = 0; i < lp; ++i) {
+                    const uint64_t ep = ent_p[bp + i];
+                    const uint64_t C = join_class<DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), &nk, &v);
+                    if (!C) continue;
+                    bool big;
+                    const uint64_t word = join_entry(ep >> 20, C, &big);
+                    join_put_entry(j, sd_q, off++, nd_q, word);
+                    nb += big;
+                    acc[0] += 1;
+                    acc[1] += nk;
+                    acc[2] += nk * v;
+                }
+                if (shortp && carry) j.cur_dst[q] = off;
+                uint64_t slot = wave_reserve(j.n_out, nb, lane);   // (big counts: one returning atomic if the wave has any)
+                for (uint32_t i = 0; nb && i < lp; ++i) {
+                    const uint64_t ep = ent_p[bp + i];
+                    const uint64_t C = join_class<DECODE>(j, !swap, q, ep, join_find(ent_s, bs, ls, ep >> 20), &nk, &v);
+                    if (C >= TAB_CMAX) join_put_big(j, slot++, ((uint64_t)q << TAB_RBITS) | (ep >> 20), C);
                 }
             }
         }
@@ -217,7 +314,16 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
             const uint64_t *ent_p = p_is_a ? j.a.ent : j.b.ent, *ent_s = p_is_a ? j.b.ent : j.a.ent;
             const uint64_t bp = p_is_a ? ba : bb, bs = p_is_a ? bb : ba;
             const uint32_t LP = p_is_a ? la : lb, LS = p_is_a ? lb : la;
-            if (MODE != JM_COMPARE && (LP == 0 || (j.op == JOIN_INTERSECT && LS == 0))) continue;
+            // the result as a table: the pair's count / running offset, wave-uniform; it carries
+            // across the ranges of a split bucket
+            const uint32_t nd_j = readlane32(nd_q, jx);
+            const uint64_t sd_j = readlane64(sd_q, jx);
+            uint32_t woff = readlane32(off_q, jx), pc = 0;
+            if (MODE != JM_COMPARE && (LP == 0 || (j.op == JOIN_INTERSECT && LS == 0))) {
+                if (MODE == JM_TCOUNT && lane == 0) j.nd_dst[qj] = nd_j;
+                if (carry && lane == 0) j.cur_dst[qj] = woff;
+                continue;
+            }
             const uint32_t s0 = join_depth0(LS);
             uint32_t s = s0;
             uint64_t t = 0;
@@ -295,7 +401,7 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                         const uint32_t p = o + u * 64 + lane;
                         e[u] = p < LP ? ent_p[bp + p] : 0;
                     }
-                    uint32_t nt = 0;
+                    uint32_t nt = 0, nb = 0;
 #pragma unroll
                     for (uint32_t u = 0; u < JOIN_UNROLL; ++u) {
                         ev[u] = 0;
@@ -313,11 +419,41 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                             slot = (slot + 1) & (used - 1);
                         }
                         uint64_t keys[2], v;
+                        if (MODE == JM_TCOUNT || MODE == JM_TWRITE) {
+                            uint32_t nk;
+                            const uint64_t C = join_class<DECODE>(j, p_is_a, qj, e[u], es, &nk, &v);
+                            if (MODE == JM_TCOUNT) {
+                                pc += C != 0;
+                                mine += C >= TAB_CMAX;
+                            } else if (C) {
+                                ev[u] = C;
+                                nt += 1;
+                                nb += C >= TAB_CMAX;
+                                acc[0] += 1;
+                                acc[1] += nk;
+                                acc[2] += nk * v;
+                            }
+                            continue;
+                        }
                         const uint32_t n = join_visit<MODE, DECODE>(j, p_is_a, qj, e[u], es, acc, keys, &v);
                         if (MODE == JM_COUNT) mine += n;
                         if (MODE == JM_WRITE) {
                             ev[u] = n ? v : 0;
                             nt += n;
+                        }
+                    }
+                    if (MODE == JM_TWRITE) {                     // one scan over the lanes that hold a result
+                        const uint32_t incl = wave_incl_sum(nt);
+                        uint32_t off = woff + (incl - nt);
+                        woff += readlane32(incl, 63);
+                        uint64_t slot = wave_reserve(j.n_out, nb, lane);   // (one returning atomic if the round has big counts)
+#pragma unroll
+                        for (uint32_t u = 0; u < JOIN_UNROLL; ++u) {
+                            if (!ev[u]) continue;
+                            bool big;
+                            const uint64_t word = join_entry(e[u] >> 20, ev[u], &big);
+                            join_put_entry(j, sd_j, off++, nd_j, word);
+                            if (big) join_put_big(j, slot++, ((uint64_t)qj << TAB_RBITS) | (e[u] >> 20), ev[u]);
                         }
                     }
                     if (MODE == JM_WRITE) {
@@ -340,6 +476,11 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
                 }
                 if (!join_next(s0, &s, &t)) break;
             }
+            if (MODE == JM_TCOUNT) {                             // the wave's count of the pair, stored once
+                const uint32_t tot = join_wave_sum(pc);
+                if (lane == 0) j.nd_dst[qj] = nd_j + tot;
+            }
+            if (carry && lane == 0) j.cur_dst[qj] = woff;
         }
     }
     if (MODE == JM_COMPARE) {
@@ -348,9 +489,15 @@ __global__ __launch_bounds__(64 * JOIN_WAVES) void tab_join_kernel(const TabJoin
             const uint64_t x = wave_sum(acc[i]);
             if (lane == 0 && x) atomicAdd(&j.sums[i], (unsigned long long)x);
         }
-    } else if (MODE == JM_COUNT) {
+    } else if (MODE == JM_COUNT || MODE == JM_TCOUNT) {          // (TCOUNT: the result's big counts)
         mine = wave_sum(mine);
         if (lane == 0 && mine) atomicAdd(j.n_out, (unsigned long long)mine);
+    } else if (MODE == JM_TWRITE) {                              // the result's statistics: classes, Map keys, their sum
+#pragma unroll
+        for (uint32_t i = 0; i < 3; ++i) {
+            const uint64_t x = wave_sum(acc[i]);
+            if (lane == 0 && x) atomicAdd(&j.stats[i], (unsigned long long)x);
+        }
     }
 }
 
@@ -379,6 +526,25 @@ hipError_t launch_tab_join_count(const TabJoin &j, hipStream_t s) {
 
 hipError_t launch_tab_join_write(const TabJoin &j, hipStream_t s) {
     hipLaunchKernelGGL((tab_join_kernel<JM_WRITE, true>), dim3(JOIN_GRID), dim3(64 * JOIN_WAVES), 0, s, j);
+    return hipGetLastError();
+}
+
+// the result as a table: nd_dst[q], then (after the scan of nd_dst) the entries,
+// the big list and the statistics.  Neither needs the keys, so a plain table
+// decodes nothing in either.
+hipError_t launch_tab_join_tcount(const TabJoin &j, hipStream_t s) {
+    if (join_plain(j))
+        hipLaunchKernelGGL((tab_join_kernel<JM_TCOUNT, false>), dim3(JOIN_GRID), dim3(64 * JOIN_WAVES), 0, s, j);
+    else
+        hipLaunchKernelGGL((tab_join_kernel<JM_TCOUNT, true>), dim3(JOIN_GRID), dim3(64 * JOIN_WAVES), 0, s, j);
+    return hipGetLastError();
+}
+
+hipError_t launch_tab_join_twrite(const TabJoin &j, hipStream_t s) {
+    if (join_plain(j))
+        hipLaunchKernelGGL((tab_join_kernel<JM_TWRITE, false>), dim3(JOIN_GRID), dim3(64 * JOIN_WAVES), 0, s, j);
+    else
+        hipLaunchKernelGGL((tab_join_kernel<JM_TWRITE, true>), dim3(JOIN_GRID), dim3(64 * JOIN_WAVES), 0, s, j);
     return hipGetLastError();
 }
 

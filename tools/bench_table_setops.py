@@ -12,8 +12,13 @@ Per size, in one process:
             do before (sorts and decodes all of A, then scans B's bucket once
             per key)
   compare   kmer_table_compare(a, b, 1, 1)
-  subtract  kmer_table_setop_device(a, b, SUBTRACT, 1, 1)
-Required: compare faster than route.  compare / floor is reported, not gated.
+  subtract  kmer_table_setop_device(a, b, SUBTRACT, 1, 1), and UNION likewise
+  into      kmer_table_setop_into(a, b, SUBTRACT / UNION, 1, 1, dst): the same
+            operations with a table as their result, checked against compare
+            (keys, totals) and, for UNION, digest(dst) = digest(a) + digest(b)
+Required: compare faster than route.  compare / floor is reported, not gated;
+so is into against the device setop of the same operation (expected: clearly
+below it) and against the floor.
 A step that does not fit device memory is reported as such and skipped.
 Timing: each call between two HIP events on the caller's stream; every call
 ends in a synchronise of the context's stream, so the events enclose the whole
@@ -50,7 +55,7 @@ def table(native, first, reads, k=31):
     return ctr
 
 
-def run(native, reads, repeats, rows, skip_route=False):
+def run(native, reads, repeats, rows, skip_route=False, into_only=False):
     import torch
     a, b = table(native, 0, reads), table(native, reads // 2, reads)
     ca, ka, ta = a.table_stats()
@@ -67,7 +72,7 @@ def run(native, reads, repeats, rows, skip_route=False):
     assert (cmp["keys_a"], cmp["total_a"], cmp["keys_b"], cmp["total_b"]) == (ka, ta, kb, tb), "compare != table_stats"
     c = stat(cms)
     route = None
-    if not skip_route:
+    if not skip_route and not into_only:
         try:
             def existing():
                 d_keys, _, n = a.table_extract_device(1, 0)
@@ -88,14 +93,46 @@ def run(native, reads, repeats, rows, skip_route=False):
                     route_over_compare=route["ms_median"] / c["ms_median"] if route else None,
                     required="compare faster than the route", met=bool(c["ms_median"] < route["ms_median"]) if route else None,
                     jaccard=cmp["jaccard"], keys_both=cmp["keys_both"]))
-    try:
-        sms, (_, _, n) = timed(lambda: a.table_setop_device(b, native.SETOP_SUBTRACT), repeats)
-        assert n == ka - cmp["keys_both"], "|SUBTRACT| != keys_a - keys_both"
-        s = stat(sms)
-        emit(rows, dict(base, call="kmer_table_setop_device(SUBTRACT)", keys_out=int(n), **s,
-                        route_over_subtract=route["ms_median"] / s["ms_median"] if route else None))
-    except native.KmerError as e:
-        emit(rows, dict(base, call="kmer_table_setop_device(SUBTRACT)", skipped="does not fit: %s" % str(e)[:120]))
+    # the device setops (sorted key bytes with counts), then the same operations with a table as their
+    # result (no sort, no decode) on the same tables: the device setop of the operation is the baseline
+    base_ms = {}
+    sizes = {"SUBTRACT": ka - cmp["keys_both"], "UNION": ka + kb - cmp["keys_both"]}
+    ops = (("SUBTRACT", native.SETOP_SUBTRACT), ("UNION", native.SETOP_UNION))
+    for name, op in ops:
+        call = "kmer_table_setop_device(%s)" % name
+        if into_only:
+            continue
+        try:
+            sms, (_, _, n) = timed(lambda: a.table_setop_device(b, op), repeats)
+            assert n == sizes[name], "|%s| != what compare gives" % name
+            s = stat(sms)
+            base_ms[name] = s["ms_median"]
+            emit(rows, dict(base, call=call, keys_out=int(n), **s,
+                            route_over_subtract=route["ms_median"] / s["ms_median"] if route and name == "SUBTRACT" else None))
+        except native.KmerError as e:
+            emit(rows, dict(base, call=call, skipped="does not fit: %s" % str(e)[:120]))
+    dst = native.Counter(k=a.k, prefix=b"", flags=native.FLAG_UNORDERED)
+    digest_ab = (a.table_digest() + b.table_digest()) & ((1 << 64) - 1)
+    for name, op in ops:
+        call = "kmer_table_setop_into(%s)" % name
+        try:
+            ims, (cd, kd, td) = timed(lambda: a.table_setop_into(b, op, dst), repeats)
+        except native.KmerError as e:
+            emit(rows, dict(base, call=call, skipped="does not fit: %s" % str(e)[:120]))
+            continue
+        assert kd == sizes[name], "keys of %s into != what compare gives" % name
+        if name == "SUBTRACT":
+            assert td == ta - cmp["shared_a"], "total of SUBTRACT into != total_a - shared_a"
+        else:
+            assert td == ta + tb, "total of UNION into != total_a + total_b"
+            assert dst.table_digest() == digest_ab, "digest(UNION) != digest(a) + digest(b)"
+        i = stat(ims)
+        emit(rows, dict(base, call=call, entries_out=int(cd), keys_out=int(kd), **i,
+                        into_over_floor=i["ms_median"] / floor["ms_median"],
+                        setop_device_over_into=base_ms[name] / i["ms_median"] if name in base_ms else None,
+                        expected="clearly below the device setop of the same operation",
+                        met=bool(i["ms_median"] < base_ms[name]) if name in base_ms else None))
+    dst.close()
     a.close()
     b.close()
 
@@ -105,6 +142,8 @@ def main():
     ap.add_argument("--reads", type=int, nargs="*", default=[2_000_000])
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--skip-route", action="store_true", help="leave out the extract + lookup route (memory)")
+    ap.add_argument("--into-only", action="store_true",
+                    help="floor, compare and kmer_table_setop_into only: no route, no device setops (memory)")
     ap.add_argument("--out", default=None, help="also write the JSON lines to this file")
     args = ap.parse_args()
 
@@ -114,7 +153,7 @@ def main():
     assert torch.cuda.is_available(), "bench_table_setops needs a GPU"
     rows = []
     for reads in args.reads:
-        run(native, reads, args.repeats, rows, args.skip_route)
+        run(native, reads, args.repeats, rows, args.skip_route, args.into_only)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
