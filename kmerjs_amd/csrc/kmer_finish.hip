@@ -115,7 +115,7 @@ kmer_status bucket_heads(kmer_ctx *c, uint64_t n, bool partial) {
             HIPCHK(c, c->bcur.ensure((uint64_t)BKT_MAX * BKT_CUR_STRIDE, s));
             HIPCHK(c, hipMemsetAsync(c->bcur.p, 0, (uint64_t)BKT_MAX * BKT_CUR_STRIDE * sizeof(uint32_t), s));
         }
-        HIPCHK(c, launch_bucket_onepass(c->rkey32.p, n, invalid, shift, nb, nblk, (uint32_t)cap, c->bcur.p, c->pkey16.p,
+        HIPCHK(c, launch_bucket_onepass(c->rkey32.p, n, invalid, shift, nb, (uint32_t)cap, c->bcur.p, c->pkey16.p,
                                         c->ridx2.p, c->hmark.p, c->d_err, stamp, s));
         HIPCHK(c, launch_bucket_heads(c->pkey16.p, c->ridx2.p, nullptr, nb, shift, c->hmark.p, c->hcnt.p, c->bcur.p,
                                       (uint32_t)cap, n, c->d_err, s));

@@ -453,14 +453,17 @@ hipError_t launch_heads_wide(const uint64_t *shi, const uint64_t *slo, const uin
 // bucket finish (u32 keys of <= BKT_LOW + 11 bits)
 constexpr uint32_t BKT_LOW = 14;             // keys per bucket table: 2^14 (128 KiB of LDS: min rank, count)
 constexpr uint32_t BKT_MAX = 2048;           // buckets (keys of <= BKT_LOW + 11 bits)
-constexpr uint32_t BKT_EPB_HOST = 4096;      // elements per partition block (= BKT_EPB)
+constexpr uint32_t BKT_EPB_HOST = 4096;      // elements per partition block of the counted route (= BKT_EPB)
+constexpr uint32_t BKT_OP_EPB_HOST = 8192;   // ... of the one-pass route (= BKT_OP_EPB)
 constexpr uint32_t BKT_CUR_STRIDE = 32;      // one-pass partition: one bucket cursor per 128-byte line
 // the fixed region of a bucket on the one-pass route: 1.5 x the mean bucket
-// size + one block (a bucket past it sets ERR_BKT_CAP: the counted route redoes the finish)
-inline uint64_t bucket_cap(uint64_t n, uint32_t nb) { return (n + nb - 1) / nb * 3 / 2 + BKT_EPB_HOST; }
+// size + one block of that route, so that a finish of up to one block fits
+// whatever its keys are (a bucket past it sets ERR_BKT_CAP: the counted route
+// redoes the finish)
+inline uint64_t bucket_cap(uint64_t n, uint32_t nb) { return (n + nb - 1) / nb * 3 / 2 + BKT_OP_EPB_HOST; }
 hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                                 uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
-                                 uint8_t *hmark, unsigned int *err, uint64_t *stamp, hipStream_t s);
+                                 uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank, uint8_t *hmark,
+                                 unsigned int *err, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_hist(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
                               uint32_t nblk, uint32_t *H, uint8_t *hmark, uint64_t *stamp, hipStream_t s);
 hipError_t launch_bucket_offsets(const uint32_t *H, uint32_t nb, uint32_t nblk, uint32_t *Hs, uint32_t *btot,

@@ -2640,9 +2640,12 @@ constexpr uint32_t BKT_EPB = 4096;           // elements per partition block
 // never cleared.  The marks of all ranks are a quarter of hcnt's bytes to
 // clear, to scatter into from every XCD and to read twice.
 constexpr uint32_t HMARK_FULL = 255;
-// clear the marks of a partition block's ranks (bucket_heads sets the heads')
+// clear the marks of a partition block's ranks (bucket_heads sets the heads'):
+// EPB ranks by TPB threads, 16 marks each (the counted route's blocks: 4,096
+// by 256; the one-pass route's: 8,192 by 512)
+template <uint32_t EPB, uint32_t TPB>
 __device__ __forceinline__ void clear_head_marks(uint8_t *hmark, uint64_t base, uint64_t n) {
-    static_assert(BKT_EPB == 16 * 256, "16 marks per thread");
+    static_assert(EPB == 16 * TPB, "16 marks per thread");
     const uint64_t i = base + 16 * threadIdx.x;
     if (i + 16 <= n) *(uint4 *)(hmark + i) = make_uint4(0, 0, 0, 0);
     else for (uint64_t t = i; t < n; ++t) hmark[t] = 0;
@@ -2661,7 +2664,7 @@ __global__ __launch_bounds__(256) void bucket_hist_kernel(const uint32_t *key, u
     for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[b] = 0;
     __syncthreads();
     const uint64_t base = (uint64_t)blockIdx.x * BKT_EPB;
-    clear_head_marks(hmark, base, n);
+    clear_head_marks<BKT_EPB, 256>(hmark, base, n);
 #pragma unroll 4
     for (uint32_t j = threadIdx.x; j < BKT_EPB; j += 256) {
         const uint64_t i = base + j;
@@ -2820,6 +2823,12 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const uint32_t *key
 }
 
 constexpr uint32_t BKT_SKIP = 0x80000000u;   // one-pass partition: a run that did not fit its bucket's region
+// One-pass partition: elements and threads per block (16 keys per thread, as
+// the counted kernels; twice their block, so that a bucket's cursor takes half
+// the claims and a block's run in a bucket is twice as long: 32 entries at C2,
+// 64 B of pkey and 128 B of prank).  72 KiB of LDS: two blocks per CU, 512 at
+// once on the device -- C2's 322 are all resident.
+constexpr uint32_t BKT_OP_EPB = 8192, BKT_OP_TPB = 512;
 
 // One-pass partition (fixed regions): the work of bucket_hist, bucket_offsets
 // and bucket_scatter in one launch.  bucket_heads_kernel applies only
@@ -2832,41 +2841,50 @@ constexpr uint32_t BKT_SKIP = 0x80000000u;   // one-pass partition: a run that d
 // totals (bucket_heads_kernel reads them and returns them to 0).  A run that
 // would end past the region is not written: ERR_BKT_CAP, and the host redoes
 // the finish with the counted kernels.  nb * cap < 2^31 (launcher).
-__global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
-                                                             uint32_t shift, uint32_t nb, uint32_t cap, uint32_t *cur,
-                                                             uint16_t *pkey, uint32_t *prank, uint8_t *hmark,
-                                                             unsigned int *err, uint64_t *stamp) {
+__global__ __launch_bounds__(BKT_OP_TPB) void bucket_onepass_kernel(const uint32_t *key, uint64_t n, uint32_t invalid,
+                                                                    uint32_t shift, uint32_t nb, uint32_t cap,
+                                                                    uint32_t *cur, uint16_t *pkey, uint32_t *prank,
+                                                                    uint8_t *hmark, unsigned int *err, uint64_t *stamp) {
     stamp_now(stamp, STAMP_FINISH_START);
+    constexpr uint32_t T = BKT_OP_TPB, KPT = BKT_OP_EPB / T, BPT = BKT_MAX / T, NW = T / 64;
+    static_assert(BKT_OP_EPB == BKT_OP_EPB_HOST && BKT_MAX % T == 0, "the region rule's block; whole buckets per thread");
     __shared__ uint32_t cnt[BKT_MAX];          // per bucket: count, then local start, then global position
-    __shared__ uint32_t skey[BKT_EPB];
-    __shared__ uint32_t srank[BKT_EPB];
-    __shared__ uint32_t wtot[4];
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * BKT_EPB;
-    clear_head_marks(hmark, base, n);
-    uint32_t kk[BKT_EPB / 256], li[BKT_EPB / 256];
+    __shared__ uint32_t skey[BKT_OP_EPB];
+    __shared__ uint32_t srank[BKT_OP_EPB];
+    __shared__ uint32_t wtot[NW];
+    const uint64_t base = (uint64_t)blockIdx.x * BKT_OP_EPB;
+    // a thread's keys loaded first of all and before any is used, at an index
+    // clamped to the last key (n >= 1: the launcher): written as `i < n ?
+    // key[i] : invalid` in the loop below, each load stood in a branch of its
+    // own with a full vmcnt wait in front of its LDS add -- 16 dependent round
+    // trips per wave where one does (the kernel's assembly and its counters:
+    // a wave waited for 77 % of its cycles)
+    uint32_t kk[KPT], li[KPT];
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
-        const uint64_t i = base + u * 256 + threadIdx.x;
-        kk[u] = i < n ? key[i] : invalid;
+    for (uint32_t u = 0; u < KPT; ++u) kk[u] = key[min(base + u * T + threadIdx.x, n - 1)];
+    for (uint32_t b = threadIdx.x; b < nb; b += T) cnt[b] = 0;
+    __syncthreads();
+    clear_head_marks<BKT_OP_EPB, T>(hmark, base, n);
+#pragma unroll
+    for (uint32_t u = 0; u < KPT; ++u) {
+        if (base + u * T + threadIdx.x >= n) kk[u] = invalid;
         li[u] = kk[u] != invalid ? atomicAdd(&cnt[kk[u] >> shift], 1u) : 0u;
     }
     __syncthreads();
-    // exclusive scan of the bucket counts (nb <= BKT_MAX, <= 8 per thread)
-    uint32_t loc[BKT_MAX / 256], sum = 0;
+    // exclusive scan of the bucket counts (nb <= BKT_MAX, <= BPT per thread)
+    uint32_t loc[BPT], sum = 0;
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
-        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+    for (uint32_t u = 0; u < BPT; ++u) {
+        const uint32_t b = threadIdx.x * BPT + u;
         loc[u] = b < nb ? cnt[b] : 0u;
         sum += loc[u];
     }
     // the claims: this block's run of each owned bucket, region-relative; in
     // flight during the scan and the placement
-    uint32_t gpos[BKT_MAX / 256];
+    uint32_t gpos[BPT];
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
-        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+    for (uint32_t u = 0; u < BPT; ++u) {
+        const uint32_t b = threadIdx.x * BPT + u;
         gpos[u] = b < nb && loc[u] ? atomicAdd(cur + (uint64_t)b * BKT_CUR_STRIDE, loc[u]) : 0u;
     }
     const uint32_t incl = wave_incl_sum(sum);
@@ -2874,22 +2892,24 @@ __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key
     __syncthreads();
     uint32_t pre = incl - sum;
     for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) pre += wtot[w];
-    uint32_t lst[BKT_MAX / 256];
+    uint32_t lst[BPT];
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
-        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+    for (uint32_t u = 0; u < BPT; ++u) {
+        const uint32_t b = threadIdx.x * BPT + u;
         lst[u] = pre;                            // local start of bucket b in skey / srank
         if (b < nb) cnt[b] = pre;
         pre += loc[u];
     }
-    const uint32_t valid = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    uint32_t valid = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < NW; ++w) valid += wtot[w];
     __syncthreads();
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_EPB / 256; ++u) {
+    for (uint32_t u = 0; u < KPT; ++u) {
         if (kk[u] != invalid) {
             const uint32_t p = cnt[kk[u] >> shift] + li[u];
             skey[p] = kk[u];
-            srank[p] = (uint32_t)(base + u * 256 + threadIdx.x);
+            srank[p] = (uint32_t)(base + u * T + threadIdx.x);
         }
     }
     // every wave has read its local starts before cnt[] is rewritten (the
@@ -2899,8 +2919,8 @@ __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key
     // element e of bucket b goes to cnt[b] + e), or BKT_SKIP
     bool over = false;
 #pragma unroll
-    for (uint32_t u = 0; u < BKT_MAX / 256; ++u) {
-        const uint32_t b = threadIdx.x * (BKT_MAX / 256) + u;
+    for (uint32_t u = 0; u < BPT; ++u) {
+        const uint32_t b = threadIdx.x * BPT + u;
         if (b < nb && loc[u]) {
             const bool fits = (uint64_t)gpos[u] + loc[u] <= cap;
             cnt[b] = fits ? b * cap + gpos[u] - lst[u] : BKT_SKIP;
@@ -2910,7 +2930,7 @@ __global__ __launch_bounds__(256) void bucket_onepass_kernel(const uint32_t *key
     if (over) atomicOr(err, ERR_BKT_CAP);
     __syncthreads();
     const uint32_t lo_mask = (1u << shift) - 1u;
-    for (uint32_t e = threadIdx.x; e < valid; e += 256) {
+    for (uint32_t e = threadIdx.x; e < valid; e += T) {
         const uint32_t k = skey[e], b = k >> shift;
         const uint32_t c = cnt[b];
         if (c == BKT_SKIP) continue;
@@ -3764,12 +3784,14 @@ hipError_t launch_bucket_scatter(const uint32_t *key, uint64_t n, uint32_t inval
     return hipGetLastError();
 }
 hipError_t launch_bucket_onepass(const uint32_t *key, uint64_t n, uint32_t invalid, uint32_t shift, uint32_t nb,
-                                 uint32_t nblk, uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank,
-                                 uint8_t *hmark, unsigned int *err, uint64_t *stamp, hipStream_t s) {
+                                 uint32_t cap, uint32_t *cur, uint16_t *pkey, uint32_t *prank, uint8_t *hmark,
+                                 unsigned int *err, uint64_t *stamp, hipStream_t s) {
+    if (n == 0) return hipSuccess;               // (the kernel clamps its key loads to key[n - 1])
     // (region addresses are 32-bit, and BKT_SKIP must not be one of them)
-    if (nb == 0 || nb > BKT_MAX || (uint64_t)nb * cap > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bucket_onepass_kernel, dim3(nblk), dim3(256), 0, s, key, n, invalid, shift, nb, cap, cur, pkey,
-                       prank, hmark, err, stamp);
+    const uint64_t nblk = (n + BKT_OP_EPB - 1) / BKT_OP_EPB;
+    if (nb == 0 || nb > BKT_MAX || (uint64_t)nb * cap > 0x7FFFFFFFull || nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bucket_onepass_kernel, dim3((uint32_t)nblk), dim3(BKT_OP_TPB), 0, s, key, n, invalid, shift, nb, cap,
+                       cur, pkey, prank, hmark, err, stamp);
     return hipGetLastError();
 }
 hipError_t launch_bucket_heads(const uint16_t *pkey, const uint32_t *prank, const uint32_t *bbase, uint32_t nb,

@@ -23,7 +23,8 @@ agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(out + "/pmc*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r.get("Kernel_Name", "")
-        if "scan_planes" not in k and "hit_kernel" not in k and "::emit_kernel" not in k:
+        if not any(n in k for n in ("scan_planes", "hit_kernel", "::emit_kernel", "bucket_onepass_kernel",
+                                    "bucket_heads_kernel")):
             continue
         agg[k.split("(")[0][-40:]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, d in agg.items():
